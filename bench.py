@@ -1,12 +1,25 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio-seconds per second for encode()+decode() (RTF^-1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over one batch of synthetic 16 kHz audio already resident in HBM: 32 utterances x
 10 s per GPU (BASELINE.json's metric shape; SURVEY.md 8d inputs: 0.1 * N(0,1), torch.Generator seed 1234, one draw per
 utterance in order).  Weights: the closed-form synthetic checkpoint (291 M parameters, random-init statistics).
+
+A plain run does only what `value` needs: set-up (which ends with one untimed call of the step), W warm-up steps, EXACTLY K timed steps of the `value` measurement
+(scatter_gather below; independent_shards with --no-dist), the outputs of the last timed step if --dump-outputs DIR is
+given, and the JSON line.  `--dump-outputs DIR` writes what a caller of the timed path receives from its last step, as
+float32 arrays: DIR/codes.npy (utterances x code groups x frames) and DIR/waveforms.npy (utterances x samples); past
+64 MB in all, waveforms.npy holds a fixed seeded sample of the rows, whose indices are in DIR/waveform_rows.npy.
+The inputs are the same on every run with the same arguments, so that two builds can be compared output for output.
+
+If the scatter_gather measurement fails at N > 1, a plain run exits non-zero: it has no other figure to report (with
+--full the independent-shard figure becomes `value` and the error goes to `scatter_gather_error`).
+
+Everything below beyond `value` runs with --full only: the extras' own options (--cpu-baseline, --cpu-threads, --no-timer,
+--no-inflight, --other-configs) apply there, and without --full an option that asks for an extra is an error.
 
 Two measurements, each W warm-up steps then EXACTLY K timed steps bracketed by barrier + device sync, MAX over ranks:
   scatter_gather  (`value`)  — BASELINE.json configs[3]: rank 0 owns all N x 32 utterances in its HBM; a step is
@@ -285,6 +298,26 @@ def git_commit():
         return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the codes and waveforms of the last timed step, as a caller of the timed path receives them, in
+    float32 (codes < 2^24 are exact).  Past DUMP_BYTES in all, a fixed seeded sample of the waveform rows is kept, and
+    their indices go to waveform_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    codes = np.stack([c.float().cpu().numpy() for c in out["codes_list"]])
+    wavs = np.stack([w.float().cpu().numpy() for w in out["syn_wav_list"]])
+    room = max(DUMP_BYTES - codes.nbytes, 0) // max(wavs[0].nbytes, 1)
+    if room < wavs.shape[0]:
+        rows = np.sort(np.random.default_rng(1234).choice(wavs.shape[0], size=int(room), replace=False))
+        wavs = wavs[rows]
+        np.save(os.path.join(path, "waveform_rows.npy"), rows.astype(np.float32))
+    np.save(os.path.join(path, "codes.npy"), codes.astype(np.float32))
+    np.save(os.path.join(path, "waveforms.npy"), wavs.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -293,17 +326,34 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--precision", default="mixed", choices=["fp32", "mixed", "mixed_f32", "bf16", "fp8", "fp8_fc1", "f16s"])
-    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "small", "full", "off"],
-                    help="sample: B=8 x 10 s, BASELINE.json configs[1]'s shape (~25 s of CPU work); small: 2 utterances "
-                         "(~15 s); full: B=8 and B=32 as BASELINE.md 2 (minutes)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the CPU baseline (default: every visible core)")
-    ap.add_argument("--no-timer", action="store_true", help="no per-launch event pairs (no roofline object)")
+    # the extras' own options take effect with --full; without it only the settings that switch an extra off are accepted
+    ap.add_argument("--cpu-baseline", default=None, choices=["sample", "small", "full", "off"],
+                    help="(--full) sample, the default: B=8 x 10 s, BASELINE.json configs[1]'s shape (~25 s of CPU work); small: "
+                         "2 utterances (~15 s); full: B=8 and B=32 as BASELINE.md 2 (minutes)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="(--full) host threads of the CPU baseline (default: every visible core)")
+    ap.add_argument("--no-timer", action="store_true", help="(--full) no per-launch event pairs (no roofline object)")
     ap.add_argument("--no-dist", action="store_true", help="N=1 only: skip the process group and the scatter/gather measurement")
     ap.add_argument("--no-inflight", action="store_true",
-                    help="skip the two-batches-in-flight extra (profiling passes: only serial steps in the kernel trace)")
-    ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
-                    help="the other BASELINE.json configs after the metric (auto: N=1 and the default workload / preset)")
+                    help="(--full) skip the two-batches-in-flight extra (profiling passes: only serial steps in the kernel trace)")
+    ap.add_argument("--other-configs", default=None, choices=["auto", "on", "off"],
+                    help="(--full) the other BASELINE.json configs after the metric (auto, the default: N=1 and the default "
+                         "workload / preset)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond `value`: CPU baseline, answer check, independent-shard and two-in-flight "
+                         "measurements, roofline, other configs (a plain run times the `value` measurement only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's codes and waveforms to DIR/*.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if not args.full:  # the extras: --full only
+        asked = [f"--cpu-baseline {args.cpu_baseline}" if args.cpu_baseline not in (None, "off") else None,
+                 "--cpu-threads" if args.cpu_threads else None,
+                 f"--other-configs {args.other_configs}" if args.other_configs not in (None, "off") else None]
+        asked = [a for a in asked if a]
+        if asked:
+            ap.error(f"{', '.join(asked)} asks for an extra of --full (a plain run times `value` only): add --full")
+        args.cpu_baseline, args.no_timer, args.no_inflight, args.other_configs = "off", True, True, "off"
+    else:
+        args.cpu_baseline, args.other_configs = args.cpu_baseline or "sample", args.other_configs or "auto"
 
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -377,7 +427,7 @@ def main():
         cpu_res, first = cpu_baseline(gp, sd, shapes, args.seconds, threads, timed=1 if args.cpu_baseline == "small" else 3)
         cpu_res["cores_visible"], cpu_res["cpu_quota"] = visible, quota
         expect = {"source": "oracle/ref_cpu.py (CPU, fp32)", "codes": first["codes"], "wav": first["wav"]}
-    else:
+    elif args.full:
         r0 = model.encode(mine[:1], overlap_seconds=10, device=dev)["codes_list"]
         w0 = model.decode(r0, overlap_seconds=10, device=dev)["syn_wav_list"]
         expect = {"source": "utterance 0 alone on the GPU (batch independence)", "codes": [r0[0].long().cpu()],
@@ -389,12 +439,14 @@ def main():
     # profiles/r02_code_agreement.txt: a latent within 1e-6 of a rounding boundary): against IT up to 2 of utterance 0's 1 000
     # codes may differ (a wrong kernel flips hundreds; the count is on the line and has been 0 on every box); against the
     # GPU's own single-utterance run nothing may differ (batch independence is bit-exact)
-    allowed = 2 if expect["source"].startswith("oracle") else 0
+    allowed = 2 if expect is not None and expect["source"].startswith("oracle") else 0
     parity = {}
 
     def check_answer(codes_list, wav_list):
         """codes of utterance 0 bit for bit (presets with an f32-class encoder), waveform of utterance 0 within the decode
-        tolerance; agreement over all the rows the source covers is reported."""
+        tolerance; agreement over all the rows the source covers is reported.  (--full only.)"""
+        if expect is None:
+            return
         mism = total = 0
         worst = 0.0
         for i, want in enumerate(expect["codes"]):
@@ -435,6 +487,12 @@ def main():
 
     def timed(step, check, timer):
         """W warm-ups, then exactly K steps between two fences; returns (seconds MAX over ranks, per-step ms list)."""
+        if not args.full:
+            # set-up of a plain run: one untimed call takes the first-call costs (code-object loads, workspace and
+            # collective buffers) that the extras before the `value` measurement absorb in a --full run, so that they
+            # stay out of the timed steps whatever W is
+            step()
+            fence()
         for _ in range(args.warmup):
             step()
         sampled = set(range(args.steps - 1, -1, -20)) if timer is not None else set()  # event pairs around every launch cost ~0.8 ms per sampled step
@@ -468,7 +526,7 @@ def main():
         if bad:
             raise AssertionError("bench: the answer check failed on another rank")
         per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-        return elapsed, per_step, len(sampled)
+        return elapsed, per_step, len(sampled), out
 
     # ---- measurement A: independent shards (no data-path traffic)
     def step_local():
@@ -483,9 +541,11 @@ def main():
             check_answer(out["codes_list"], out["syn_wav_list"])
 
     timer = None if args.no_timer else KernelTimer()
-    el_a, steps_a, n_sampled = timed(step_local, check_local, None if use_dist else timer)
-    res_a = {"value": round(world * args.batch * args.seconds * args.steps / el_a, 2),
-             "ms_per_step": round(1e3 * el_a / args.steps, 3), "ms_per_step_median": round(statistics.median(steps_a), 3)}
+    res_a, last_out = None, None
+    if args.full or not use_dist:  # `value` itself without the process group; an extra beside scatter_gather (--full)
+        el_a, steps_a, n_sampled, last_out = timed(step_local, check_local, None if use_dist else timer)
+        res_a = {"value": round(world * args.batch * args.seconds * args.steps / el_a, 2),
+                 "ms_per_step": round(1e3 * el_a / args.steps, 3), "ms_per_step_median": round(statistics.median(steps_a), 3)}
 
     # ---- measurement B: rank 0 scatters / gathers over RCCL (configs[3])
     res_b, b_err = None, None
@@ -503,16 +563,19 @@ def main():
                     assert len(out["codes_list"]) == world * args.batch and out["codes_list"][-1].shape[-1] == n // 1280
                     check_answer(out["codes_list"], out["syn_wav_list"])
 
-            el_b, steps_b, n_sampled = timed(step_dp, check_dp, timer)
+            el_b, steps_b, n_sampled, last_out = timed(step_dp, check_dp, timer)
             res_b = {"value": round(world * args.batch * args.seconds * args.steps / el_b, 2),
                      "ms_per_step": round(1e3 * el_b / args.steps, 3),
                      "ms_per_step_median": round(statistics.median(steps_b), 3)}
         except Exception as e:
-            if world > 1:
+            if world > 1 and res_a is not None:
                 # every rank fails or none: the error is raised collectively by RCCL; report the shard number with the reason
                 b_err = f"{type(e).__name__}: {e}"
             else:
                 raise
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out)
+    last_out = None
     # ---- measurement C (after the two metric measurements, so that it cannot warm the chip for them): the same K steps with TWO batches in flight (pipeline.InFlight: two host threads, two streams, two
     # model objects over one set of operands): what the serving loop around the path gains when consecutive batches
     # overlap.  Reported beside `value`, never as `value`: a step there is one batch at a time.
@@ -619,9 +682,9 @@ def main():
             "config": {"workload": f"batch={args.batch}x{args.seconds:g}s @16kHz per GPU ({world * args.batch} utterances in all), "
                                    f"encode()+decode(), 0.1*N(0,1) seed 1234, synthetic closed-form checkpoint (291M params)",
                        "precision": args.precision, "parallelism": par},
-            "independent_shards": res_a,
-            "two_in_flight": res_a2,
         }
+        if args.full:
+            line.update({"independent_shards": res_a, "two_in_flight": res_a2})
         if b_err:
             line["scatter_gather_error"] = b_err
         if dist_note:

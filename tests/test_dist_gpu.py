@@ -162,7 +162,7 @@ def test_bench_multi_rank_rehearsal(n):
     env.pop("SWC_LIB", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2",
-                        "--warmup", "1", "--batch", "4", "--seconds", "3", "--cpu-baseline", "off", "--no-inflight"],
+                        "--warmup", "1", "--batch", "4", "--seconds", "3", "--full", "--cpu-baseline", "off", "--no-inflight"],
                        cwd=root, env=dict(env, OMP_NUM_THREADS="3"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

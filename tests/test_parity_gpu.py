@@ -244,8 +244,11 @@ def test_window_batching_is_exact():
         assert torch.equal(a, b)
     for a, b in zip(w_ser, w_bat):
         assert torch.equal(a, b)
-    # and the oracle agrees on the codes of the long utterances
-    o = oracle("tiny")
+    # and the oracle agrees on the codes of the long utterances.  In double: one latent of utterance 0 (group 2, frame 332)
+    # lies within float32 rounding of an FSQ boundary, and the float32 oracle's code there moves with the host's BLAS and
+    # thread count (310 or 318); the float64 oracle gives every code the same on every host
+    from oracle.ref_cpu import Oracle
+    o = Oracle(PARAMS["tiny"](), state_dict("tiny"), dtype=torch.float64)
     want = o.encode([w.cpu() for w in wavs], trim=True)["codes_list"]
     for a, b in zip(c_bat, want):
         assert torch.equal(a.cpu().long(), b.long())

@@ -7,7 +7,7 @@ export SWC_COMMIT=${2:-unknown} SWC_PROFILE_TAG=$tag
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd "$R"
-python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 echo "bench done"; tail -c 600 $out/bench.json
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python3 $R/bench.py --steps 13 --warmup 3 --cpu-baseline off --no-dist --no-timer --no-inflight --other-configs off > $out/bench_under_rocprof.json 2> $out/rocprof.err )
 echo "rocprof stats done"
@@ -29,7 +29,7 @@ for k, v in (d.get('other_configs') or {}).items():
     print(json.dumps({'config': k, 'value': v.get('value'), 'ms_per_step': v.get('ms_per_step'), 'dominant': r.get('kernel'), 'achieved': r.get('achieved'), 'frac': r.get('frac'), 'other': {a: b['TFLOP/s'] for a, b in (r.get('other') or {}).items()}, 'error': v.get('error')}))
 " > $out/other_configs.jsonl
 for spec in "--precision bf16" "--precision fp8_fc1" "--precision f16s"; do
-  python3 bench.py --steps 6 --warmup 2 --cpu-baseline off --no-dist --no-inflight --other-configs off $spec 2>/dev/null | python3 -c "
+  python3 bench.py --full --steps 6 --warmup 2 --cpu-baseline off --no-dist --no-inflight --other-configs off $spec 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d.get('roofline',{})
 print(json.dumps({'args': '$spec', 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'dominant': r.get('kernel'), 'achieved': r.get('achieved'), 'frac': r.get('frac'), 'other': {k: v['TFLOP/s'] for k, v in r.get('other', {}).items()}}))" >> $out/other_configs.jsonl

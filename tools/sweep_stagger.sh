@@ -15,7 +15,7 @@ done
 for rep in 1 2; do
   for st in $1; do
     echo "== step, stagger $st"
-    SWC_LIB=$lib SWC_GEMM_STAGGER=$st python3 bench.py --steps 10 --warmup 3 --cpu-baseline off --no-dist --no-inflight --other-configs off 2>/dev/null | python3 -c "
+    SWC_LIB=$lib SWC_GEMM_STAGGER=$st python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline off --no-dist --no-inflight --other-configs off 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d.get('roofline',{})
 print(d['value'], d['ms_per_step'], r.get('kernel'), r.get('achieved'), {k:v['TFLOP/s'] for k,v in r.get('other',{}).items()})"
