@@ -132,6 +132,8 @@ int swc_gemm(const swc_gemm_args* args, void* stream);
  * 64^-0.5 through the packed weights), out: [B][T][H*64].  Rows t >= lens[b]
  * produce finite don't-care values (the caller masks them, modules.py:358,460).
  * dtype is the element type of qkv and out.
+ * Memory: all T rows of out of every utterance are written and nothing else.  q / k / v rows t >= lens[b] may be read (they
+ * must be finite) but rows t < lens[b] of out do not depend on them, bit for bit; an utterance with lens[b] == 0 is not read.
  */
 int swc_attention(const void* qkv, void* out, const int32_t* lens, int32_t B, int32_t T,
                   int32_t H, int32_t dtype, void* stream);
@@ -143,6 +145,8 @@ int swc_attention(const void* qkv, void* out, const int32_t* lens, int32_t B, in
  * row_start (NULL = padded layout, utterance b at rows b*T ..): VALID-TOKEN PACKING — utterance b's lens[b] rows of qkv and
  * out start at row row_start[b] and nothing follows them but the next utterance: ragged batches then cost their valid
  * tokens, not B x the longest row (the reference pads every row, modules.py:111-143 masks afterwards).
+ * Packed layout, memory: exactly rows row_start[b] .. row_start[b] + lens[b] - 1 of qkv are read and of out written, for every b:
+ * no row t >= lens[b] exists, and nothing behind the last utterance is touched (qkv and out may end there).
  */
 int swc_attention16(const void* qkv, void* out, const int32_t* lens, int32_t B, int32_t T, int32_t H,
                     int32_t dtype, const int32_t* row_start, void* stream);

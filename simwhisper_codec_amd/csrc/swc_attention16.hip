@@ -138,7 +138,10 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 1 : (NQT == 1 ? 4 : 2)) void
 #pragma unroll
         for (int qt = 0; qt < NQT; ++qt) {
             int q = q0 + wave * QW + qt * 16 + fr;
-            q = q < qlim ? q : qlim - 1;
+            // query columns at or beyond the length re-use the last VALID row (len > 0 wherever this runs), in the padded
+            // layout too: their results are don't-care, but the bf16 kernel's rescale test below is wave-uniform, so a
+            // padded row's scores would otherwise decide how the valid rows of its wave are rounded
+            q = q < len ? q : len - 1;
             const char* qp = base + (long)q * ldb;
 #pragma unroll
             for (int g = 0; g < 2; ++g)
