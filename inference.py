@@ -34,7 +34,7 @@ sys.path.insert(0, ROOT)
 
 from audiocodec.model import AudioCodec  # noqa: E402
 from simwhisper_codec_amd.pipeline import HostStager  # noqa: E402
-from simwhisper_codec_amd.wavio import find_audio_files, load_audio, read_pcm16, save_audio, save_pcm16  # noqa: E402
+from simwhisper_codec_amd.wavio import find_audio_files, load_audio, read_pcm, read_pcm16, save_audio, save_pcm16  # noqa: E402
 
 
 def set_logging(level="INFO"):
@@ -62,7 +62,45 @@ def build_parser():
                         "about 1 200 ten-second files per second, less than one GPU produces)")
     p.add_argument("--dist_backend", type=str, default="nccl", help="torch.distributed backend under torch.distributed.run "
                    "(nccl = RCCL; gloo moves the audio through host memory: tests)")
+    p.add_argument("--resample", type=str, default="host", choices=["host", "gpu"],
+                   help="where files that are not mono at the model's rate are converted.  host (default): on the loader "
+                        "threads (wavio.load_audio), the outputs of every earlier version.  gpu (with a CUDA device): any "
+                        "16-bit PCM WAV crosses PCIe as it is and channel mean + sample-rate conversion run in one HIP kernel "
+                        "(HostStager.to_device_pcm); other formats keep the host path.  The two sum in different orders: "
+                        "outputs of such files differ in the last bits")
     return p
+
+
+def load_file(path, target_rate, pcm16_ok, resample):
+    """What a loader thread reads from one file.  resample == "gpu": any PCM16 WAV as (int16 [n, ch], sample rate) for
+    HostStager.to_device_pcm.  Else, with pcm16_ok, a mono PCM16 file at target_rate as its int16 samples (converted on the
+    GPU: the same values).  Everything else (other widths, channels, rates, FLAC) is decoded to f32 at target_rate here."""
+    if pcm16_ok and resample == "gpu":
+        got = read_pcm(path)
+        if got is not None:
+            return got
+    elif pcm16_ok:
+        pcm = read_pcm16(path, target_rate)
+        if pcm is not None:
+            return pcm
+    return load_audio(path, target_sample_rate=target_rate).reshape(-1)
+
+
+def stage_files(stager, loaded, device, target_rate):
+    """load_file's results of one batch -> f32 device tensors at target_rate (one host-to-device copy per sample format)"""
+    pcm = [i for i, w in enumerate(loaded) if isinstance(w, tuple)]
+    if pcm:  # --resample gpu
+        out = [None] * len(loaded)
+        for i, w in zip(pcm, stager.to_device_pcm([loaded[i] for i in pcm], device, target_rate)):
+            out[i] = w
+        rest = [i for i in range(len(loaded)) if i not in pcm]
+        if rest:
+            for i, w in zip(rest, stager.to_device([loaded[i] for i in rest], device)):
+                out[i] = w
+        return out
+    if all(w.dtype == torch.int16 for w in loaded):
+        return stager.to_device_pcm16(loaded, device)
+    return stager.to_device([w if w.dtype == torch.float32 else w.to(torch.float32) * (1.0 / 32768.0) for w in loaded], device)
 
 
 def load_model(args, device):
@@ -99,10 +137,7 @@ def main(argv=None):
     on_gpu = device.type == "cuda"
 
     def load_one(path):
-        # a mono PCM16 file at the model's rate goes to the GPU as 16-bit samples (converted there: the same values);
-        # everything else (other widths, channels, rates, FLAC) is decoded to f32 here
-        pcm = read_pcm16(path, generator.input_sample_rate) if on_gpu else None
-        return pcm if pcm is not None else load_audio(path, target_sample_rate=generator.input_sample_rate).reshape(-1)
+        return load_file(path, generator.input_sample_rate, on_gpu, args.resample)
 
     def save_one(item):
         path, wav = item
@@ -115,9 +150,7 @@ def main(argv=None):
     def stage_in(cpu_wavs):
         if not on_gpu:
             return cpu_wavs
-        if all(w.dtype == torch.int16 for w in cpu_wavs):
-            return stager.to_device_pcm16(cpu_wavs, device)
-        return stager.to_device([w if w.dtype == torch.float32 else w.to(torch.float32) * (1.0 / 32768.0) for w in cpu_wavs], device)
+        return stage_files(stager, cpu_wavs, device, generator.input_sample_rate)
 
     # wall seconds per stage, summed over the threads that run them (they overlap).  The launch threads (process) do nothing but
     # launch: reading + staging runs in the loader thread, the device -> host copy + writing in the saver thread
@@ -246,8 +279,7 @@ def main_distributed(args, world):
             stager = HostStager()
 
             def load_one(path):
-                pcm = read_pcm16(path, generator.input_sample_rate)
-                return pcm if pcm is not None else load_audio(path, target_sample_rate=generator.input_sample_rate).reshape(-1)
+                return load_file(path, generator.input_sample_rate, True, args.resample)
 
             def save_one(item):
                 path, wav = item
@@ -255,10 +287,7 @@ def main_distributed(args, world):
                 save_pcm16(out, wav, sample_rate=generator.output_sample_rate)
 
             def stage_in(cpu_wavs):
-                if all(w.dtype == torch.int16 for w in cpu_wavs):
-                    return stager.to_device_pcm16(cpu_wavs, device)
-                return stager.to_device([w if w.dtype == torch.float32 else w.to(torch.float32) * (1.0 / 32768.0)
-                                         for w in cpu_wavs], device)
+                return stage_files(stager, cpu_wavs, device, generator.input_sample_rate)
 
             def load(paths):
                 return list(io.map(load_one, paths))

@@ -87,6 +87,14 @@ PLAIN = {"swc_version": ([], C.c_int), "swc_last_error": ([], C.c_char_p), "swc_
          "swc_mlp_stream_bytes": ([_I, _I], C.c_int64), "swc_convnext64_stream_bytes": ([_I, _I], C.c_int64), "swc_layer_tail_stream_bytes": ([_I, _I, _I], C.c_int64),
          "swc_proj_ln_stream_bytes": ([_I, _I], C.c_int64)}
 
+# include/swc_audio.h (the audio front end), one to one: name -> (argtypes, restype).  A table of its own: SIGNATURES, PLAIN and
+# exported_symbols() mirror include/swc.h alone
+PCM_F32, PCM_I16 = 0, 1
+AUDIO_SIGNATURES = {
+    "swc_resample_out_len": ([_L, _I, _I], C.c_int64),
+    "swc_resample": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -105,6 +113,10 @@ def load():
         fn.argtypes = argtypes
         fn.restype = C.c_int
     for name, (argtypes, restype) in PLAIN.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    for name, (argtypes, restype) in AUDIO_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -1234,12 +1234,17 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
-    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda")):
+    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
         """model.py:244-308: 30 s windows every (30 - overlap) s, keep the first 250 codes of each window,
-        concatenate, trim to len // 1280.  Returns {"codes_list": [IntTensor(G, T_i)]}."""
+        concatenate, trim to len // 1280.  Returns {"codes_list": [IntTensor(G, T_i)]}.
+        sample_rate: None = the waveforms are at input_sample_rate (the reference's contract).  An int, or one int per
+        utterance: the rate of each row; rows at another rate are converted on the GPU first (ops.resample, the whole row,
+        then windowed as usual), so row i yields ceil(input_sample_rate n_i / sr_i) // 1280 code frames."""
         B = len(wav_list)
         if B == 0:
             return {"codes_list": []}
+        if sample_rate is not None:
+            wav_list = self._to_input_rate(wav_list, sample_rate, self._resolve_device(device))
         n = [int(w.shape[-1]) if w.dim() else 0 for w in wav_list]
         dev = self._resolve_device(device)
         # Rows are independent, so the batch is assembled longest utterance first: workgroups are dispatched row by row
@@ -1268,6 +1273,28 @@ class AudioCodec(nn.Module):
                 out[i] = (torch.zeros(self.num_groups, 0, device=dev, dtype=torch.long) if allc is None
                           else allc[:, k - a, : n[i] // rate])
         return {"codes_list": out}
+
+    def _to_input_rate(self, wav_list, sample_rate, dev):
+        """encode(sample_rate=): the rows that are not at input_sample_rate, converted on the device: one swc_resample launch
+        per distinct rate, the results are rows (views) of that launch's zero-padded batch.  Rows at input_sample_rate are
+        handed on untouched."""
+        B = len(wav_list)
+        rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * B
+        if len(rates) != B or any(r < 1 for r in rates):
+            raise SwcError(f"encode: sample_rate must be a positive int or one per utterance ({B}), got {sample_rate!r}")
+        if dev.type != "cuda":
+            raise SwcError("encode(sample_rate=): the sample-rate conversion is a HIP kernel (there is no CPU fallback)")
+        out = list(wav_list)
+        by_rate = {}
+        for i, r in enumerate(rates):
+            if r != self.input_sample_rate:
+                by_rate.setdefault(r, []).append(i)
+        for r, idx in by_rate.items():
+            rows = [wav_list[i].reshape(-1).to(dev, torch.float32).contiguous() for i in idx]
+            y, n_out = ops.resample(rows, r, self.input_sample_rate)
+            for k, i in enumerate(idx):
+                out[i] = y[k, : n_out[k]]
+        return out
 
     @_on_model_device
     @torch.inference_mode()

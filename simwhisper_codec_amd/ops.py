@@ -297,6 +297,85 @@ def f32_to_pcm16(x):
     return out
 
 
+_RESAMPLE_TABLES = {}
+
+
+def resample_table(orig_freq, new_freq, device):
+    """The packed filter table of swc_resample for one pair of rates on one device, built once and kept:
+    -> dict(orig, new, width, run, taps [new, run] f32, start [new] int32 (both on the device), nnz = the largest count of
+    non-zero taps of a phase).  The values are wavio.resample_taps' own f32 numbers; per phase the window of `run` taps that
+    holds every non-zero one is kept (taps outside it are exact zeros).  Equal rates give the 1-tap identity filter."""
+    device = torch.device(device)
+    key = (int(orig_freq), int(new_freq), device.type, device.index)
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    from . import wavio
+    if int(orig_freq) == int(new_freq):
+        K, orig, new, width = torch.ones(1, 1, dtype=torch.float32), 1, 1, 0
+    else:
+        K, orig, new, width = wavio.resample_taps(orig_freq, new_freq)
+    taps = K.shape[1]
+    nz = K != 0
+    pos = torch.arange(taps)
+    first = torch.where(nz, pos, taps).amin(dim=1)
+    last = torch.where(nz, pos, -1).amax(dim=1)
+    run = max(int((last - first).max()) + 1, 1)
+    start = first.clamp(max=taps - run).clamp(min=0)
+    packed = torch.gather(K, 1, start[:, None] + torch.arange(run)[None, :])
+    t = {"orig": orig, "new": new, "width": width, "run": run, "nnz": int(nz.sum(dim=1).max()),
+         "taps": packed.contiguous().to(device), "start": start.to(torch.int32).to(device)}
+    _RESAMPLE_TABLES[key] = t
+    return t
+
+
+def resample_out_len(n_in, orig_freq, new_freq):
+    """ceil(new * n_in / orig): swc_resample_out_len of include/swc_audio.h"""
+    return int(_lib.load().swc_resample_out_len(int(n_in), int(orig_freq), int(new_freq)))
+
+
+def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None):
+    """Sample-rate conversion of a ragged batch in one launch (include/swc_audio.h swc_resample): rows = device tensors, all f32
+    1-D (mono) or all int16, [n, channels] or flat interleaved -> (out [B, cols] f32: row b holds its ceil(new n_b / orig)
+    samples and zeros behind them, the list of those lengths).  cols defaults to the longest output; a row longer than cols
+    is cut.  `out` (tests): an f32 device view [B, cols] with unit column stride to write into instead."""
+    lib = _lib.load()
+    B = len(rows)
+    if B == 0:
+        raise _lib.SwcError("resample: no rows")
+    i16 = rows[0].dtype == torch.int16
+    ch = int(channels)
+    n_in = []
+    for r in rows:
+        _chk(r, "resample row", torch.int16 if i16 else torch.float32)
+        if not r.is_contiguous():
+            raise _lib.SwcError("resample: contiguous rows expected")
+        if i16 and r.dim() == 2 and r.shape[1] != ch:
+            raise _lib.SwcError(f"resample: a row of {r.shape[1]} channels in a call for channels={ch}")
+        if (not i16 and (ch != 1 or r.dim() > 1)) or r.numel() % ch:
+            raise _lib.SwcError("resample: f32 rows are 1-D mono; int16 rows hold whole frames of `channels` samples")
+        n_in.append(r.numel() // ch)
+    device = rows[0].device
+    t = resample_table(orig_freq, new_freq, device)
+    n_out = [-(-t["new"] * n // t["orig"]) for n in n_in]
+    if out is None:
+        cols = max(n_out) if cols is None else int(cols)
+        out = torch.empty((B, cols), device=device, dtype=torch.float32)
+    else:
+        _chk(out, "resample out", torch.float32)
+        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
+            raise _lib.SwcError("resample: out must be [B, cols] with unit column stride")
+        cols = out.shape[1]
+    if cols == 0:
+        return out, n_out
+    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
+    meta = torch.tensor([r.data_ptr() for r in rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_resample(_ptr(meta[:B]), _ptr(meta[B:]), _lib.PCM_I16 if i16 else _lib.PCM_F32, ch, t["orig"], t["new"],
+                                t["width"], _ptr(t["taps"]), _ptr(t["start"]), t["run"], _ptr(out), ld, cols, B, _stream()),
+               "swc_resample")
+    return out, n_out
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""

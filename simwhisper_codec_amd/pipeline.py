@@ -119,6 +119,50 @@ class HostStager:
             dev = ops.pcm16_to_f32(dev16)
         return [dev[o:o + n] for o, n in zip(offs, lens)]
 
+    def to_device_pcm(self, items, device, target_rate):
+        """items (int16 CPU tensor [n, ch] or (n,), sample rate) as wavio.read_pcm returns them -> f32 mono device views at
+        target_rate.  Every item's 16-bit samples are packed into the pinned staging buffer and cross PCIe as ONE copy; then
+        one swc_resample launch per distinct (rate, channels) among the items that are not already mono at target_rate
+        (channel mean, scaling and filter in that kernel) and one swc_pcm16_to_f32 over the others: for those the values
+        are to_device_pcm16's, bit for bit."""
+        from . import ops
+        target_rate = int(target_rate)
+        pcm = [t if t.dim() == 2 else t.reshape(-1, 1) for t, _ in items]
+        lens = [int(t.numel()) for t in pcm]
+        plain = [i for i, (t, (_, sr)) in enumerate(zip(pcm, items)) if t.shape[1] == 1 and int(sr) == target_rate]
+        groups = {}
+        for i, (t, (_, sr)) in enumerate(zip(pcm, items)):
+            if i not in plain:
+                groups.setdefault((int(sr), int(t.shape[1])), []).append(i)
+        # the plain items first, back to back on 16-byte boundaries (one conversion over their span), the others behind
+        offs, pos, n_plain = [0] * len(pcm), 0, 0
+        for k, i in enumerate(plain + [i for idx in groups.values() for i in idx]):
+            offs[i] = pos
+            pos += (lens[i] + 7) // 8 * 8
+            if k + 1 == len(plain):
+                n_plain = pos
+        out = [None] * len(pcm)
+        if pos == 0:
+            return [torch.empty(0, dtype=torch.float32, device=device) for _ in pcm]
+        buf = getattr(self._tls, "buf16", None)
+        if buf is None or buf.numel() < pos:
+            buf = torch.empty(max(pos, 1 << 20), dtype=torch.int16).pin_memory()
+            self._tls.buf16 = buf
+        for t, o, n in zip(pcm, offs, lens):
+            buf[o:o + n].copy_(t.reshape(-1))
+        dev16 = torch.empty(pos, dtype=torch.int16, device=device)
+        dev16.copy_(buf[:pos], non_blocking=True)
+        with torch.cuda.device(device):
+            if plain:
+                dev = ops.pcm16_to_f32(dev16[:n_plain])
+                for i in plain:
+                    out[i] = dev[offs[i]:offs[i] + lens[i]]
+            for (sr, ch), idx in groups.items():
+                y, n_out = ops.resample([dev16[offs[i]:offs[i] + lens[i]] for i in idx], sr, target_rate, channels=ch)
+                for k, i in enumerate(idx):
+                    out[i] = y[k, : n_out[k]]
+        return out
+
     @staticmethod
     def _by_buffer(tensors):
         """tensors grouped by the buffer they are views of: [(base or None, [indices])].  decode() returns rows of ONE padded

@@ -145,10 +145,9 @@ def _decode_flac(path):
     return out[:n], int(sr.value), int(bits.value)
 
 
-def read_pcm16(audio_path, target_sample_rate):
-    """The common case without any host arithmetic: a mono 16-bit PCM .wav already at target_sample_rate -> its samples as an
-    int16 tensor (T,) (a copy of the file's bytes), else None.  `samples * 2^-15` (ops.pcm16_to_f32 on the GPU) is then exactly
-    what load_audio returns for the same file."""
+def _pcm16_chunks(audio_path):
+    """(fmt fields, (offset, bytes) of the data chunk, the file's bytes) of a RIFF/WAVE file holding 16-bit integer PCM,
+    else None (another container, format tag or width)."""
     if os.path.splitext(audio_path)[1].lower() != ".wav":
         return None
     with open(audio_path, "rb") as f:
@@ -163,9 +162,34 @@ def read_pcm16(audio_path, target_sample_rate):
         elif cid == b"data":
             pcm = (pos + 8, min(size, len(data) - pos - 8))
         pos += 8 + size + (size & 1)
-    if fmt is None or pcm is None or fmt[0] != 1 or fmt[1] != 1 or fmt[2] != int(target_sample_rate) or fmt[5] != 16:
+    if fmt is None or pcm is None or fmt[0] != 1 or fmt[5] != 16:
         return None
+    return fmt, pcm, data
+
+
+def read_pcm16(audio_path, target_sample_rate):
+    """The common case without any host arithmetic: a mono 16-bit PCM .wav already at target_sample_rate -> its samples as an
+    int16 tensor (T,) (a copy of the file's bytes), else None.  `samples * 2^-15` (ops.pcm16_to_f32 on the GPU) is then exactly
+    what load_audio returns for the same file."""
+    got = _pcm16_chunks(audio_path)
+    if got is None or got[0][1] != 1 or got[0][2] != int(target_sample_rate):
+        return None
+    _, pcm, data = got
     return torch.from_numpy(np.frombuffer(data, dtype="<i2", count=pcm[1] // 2, offset=pcm[0]).copy())
+
+
+def read_pcm(audio_path):
+    """Any 16-bit integer PCM .wav, whatever its rate and channel count -> (int16 tensor [n, ch], the file's interleaved
+    samples as they are, sample rate), else None (float / 8 / 24 / 32-bit WAV, FLAC: load_audio decodes those).  Channel
+    mean, scaling and sample-rate conversion are then the GPU's (ops.resample, HostStager.to_device_pcm)."""
+    got = _pcm16_chunks(audio_path)
+    if got is None or got[0][1] < 1:
+        return None
+    fmt, pcm, data = got
+    ch = int(fmt[1])
+    n = pcm[1] // 2 // ch
+    x = np.frombuffer(data, dtype="<i2", count=n * ch, offset=pcm[0]).copy()
+    return torch.from_numpy(x).reshape(n, ch), int(fmt[2])
 
 
 def save_pcm16(audio_outpath, pcm, sample_rate):
@@ -195,17 +219,14 @@ def load_audio(audio_path, target_sample_rate):
     return wav.reshape(1, 1, -1)
 
 
-def resample(wav, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
-    """Band-limited sinc interpolation with a Hann window: the algorithm torchaudio.functional.resample documents and uses
-    with its defaults (`sinc_interp_hann`, lowpass_filter_width 6, rolloff 0.99), which is what helpers.py:86 calls.
-    Restated from that published algorithm — torchaudio is absent here, so bit-parity with it is unpinned: kernel of
-    new/gcd phases x (2 width + orig/gcd) taps built in float64, float32 convolution with stride orig/gcd over the signal
-    padded by (width, width + orig/gcd), output length ceil(new * n / orig).  wav: 1-D float32 tensor."""
+def resample_taps(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The filter of `resample` as a table: -> (K f32 [new, taps], orig, new, width) with orig, new the two rates reduced by
+    their gcd, width the one-sided filter width in input samples and taps = 2 width + orig; built in float64, rounded to
+    f32 once.  out[f * new + p] = sum_t K[p, t] * xpad[f * orig + t], xpad the signal behind `width` zeros.  The same
+    values feed the host convolution below and the packed table of the GPU kernel (ops.resample)."""
     import math
     g = gcd(int(orig_freq), int(new_freq))
     orig, new = int(orig_freq) // g, int(new_freq) // g
-    if orig == new:
-        return wav
     base = min(orig, new) * rolloff
     width = math.ceil(lowpass_filter_width * orig / base)
     idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
@@ -214,10 +235,22 @@ def resample(wav, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
     t = t * math.pi
     kernel = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base / orig)
-    kernel = kernel.to(torch.float32)                                   # [new, 1, 2 width + orig]
+    return kernel.to(torch.float32).reshape(new, 2 * width + orig), orig, new, width
+
+
+def resample(wav, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """Band-limited sinc interpolation with a Hann window: the algorithm torchaudio.functional.resample documents and uses
+    with its defaults (`sinc_interp_hann`, lowpass_filter_width 6, rolloff 0.99), which is what helpers.py:86 calls.
+    Restated from that published algorithm — torchaudio is absent here, so bit-parity with it is unpinned: kernel of
+    new/gcd phases x (2 width + orig/gcd) taps built in float64 (resample_taps), float32 convolution with stride orig/gcd
+    over the signal padded by (width, width + orig/gcd), output length ceil(new * n / orig).  wav: 1-D float32 tensor."""
+    import math
+    if int(orig_freq) == int(new_freq):
+        return wav
+    kernel, orig, new, width = resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff)
     n = wav.shape[-1]
     padded = torch.nn.functional.pad(wav.reshape(1, 1, -1).to(torch.float32), (width, width + orig))
-    out = torch.nn.functional.conv1d(padded, kernel, stride=orig)       # [1, new, frames]
+    out = torch.nn.functional.conv1d(padded, kernel[:, None, :], stride=orig)   # [1, new, frames]
     out = out.transpose(1, 2).reshape(-1)
     return out[: int(math.ceil(new * n / orig))].contiguous()
 
