@@ -13,7 +13,7 @@
 // (k index 8h+j  <->  key 16 t0 + 4h + j for j < 4, 16 t1 + 4h + j - 4 otherwise).  The matching
 // V^T operand (4 consecutive keys of one channel) comes out of the row-major V tile through
 // ds_read_b64_tr_b16, the hardware transposing read.
-#include "swc_common.h"
+#include "swc_mfma.h"
 #include <type_traits>
 
 namespace {
@@ -23,21 +23,11 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16a[4] = {0u, 0u, 0u, 0u};
 
-__device__ __forceinline__ void glds16a(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
-
 // max over the lane pair (l, l ^ W), W = 16 or 32, in both lanes: operand rows swapped against a copy of themselves
-typedef unsigned u32x2_sw __attribute__((ext_vector_type(2)));
 template <int W>
 __device__ __forceinline__ float xor_max(float v) {
     const unsigned u = __float_as_uint(v);
-    const u32x2_sw r = W == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const u32x2 r = W == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
@@ -55,21 +45,9 @@ __device__ __forceinline__ f32x4 mma16(const uint4& a, const uint4& b, f32x4 c) 
                                                       *reinterpret_cast<const f16x8*>(&b), c, 0, 0, 0);
 }
 
-// two f32 -> one dword of two 16-bit values (RNE) in ONE instruction (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32): as a vector
-// conversion, not inline asm — the operands come straight from v_exp_f32, and only for instructions it knows does hipcc
-// insert the wait state a transcendental result needs before its first use (an asm form returned NaNs)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2n __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {
-    const bf16x2n r = __builtin_convertvector((f32x2){lo, hi}, bf16x2n);
-    return *reinterpret_cast<const unsigned*>(&r);
-}
-__device__ __forceinline__ unsigned pack2_f16(float lo, float hi) {
-    const f16x2 r = __builtin_convertvector((f32x2){lo, hi}, f16x2);
-    return *reinterpret_cast<const unsigned*>(&r);
-}
-
+// P is packed with the vector conversions bf16_pack2 / pack2_f16 (swc_common.h), not the asm forms of swc_mfma.h: the operands
+// come straight from v_exp_f32, and only for instructions it knows does hipcc insert the wait state a transcendental result
+// needs before its first use (an asm form returned NaNs)
 
 // KT16: keys per tile (64, or 128 for the bf16 kernel: half the fences and dependent softmax chains per key)
 // NQT: 16-query MFMA tiles per wave (2: 128 queries per workgroup; 1: 64 — half the registers, twice the waves per SIMD)
@@ -154,7 +132,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 1 : (NQT == 1 ? 4 : 2)) void
     };
 
     // ---- staging geometry (LDS-DMA, lane-linear 1 KiB per wave-instruction, swizzle on the source)
-    const unsigned smem_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem);
+    const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int l_row = lane / CPR, l_pos = lane % CPR;
     auto stage = [&](int kt, int st) {
@@ -172,8 +150,8 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 1 : (NQT == 1 ? 4 : 2)) void
             const int vu = (l_pos >> 1) ^ vrow_swz(row);
             const char* ks = rp + part + 16 * kc;
             const char* vs = rp + 2 * part + 16 * ((vu << 1) | (l_pos & 1));
-            glds16a(ok ? ks : zero, smem_base + st * 2 * TILE + inst * 1024);
-            glds16a(ok ? vs : zero, smem_base + st * 2 * TILE + TILE + inst * 1024);
+            glds16_uniform(ok ? ks : zero, smem_base + st * 2 * TILE + inst * 1024);
+            glds16_uniform(ok ? vs : zero, smem_base + st * 2 * TILE + TILE + inst * 1024);
         }
     };
     auto fence = [&]() {
@@ -332,7 +310,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 1 : (NQT == 1 ? 4 : 2)) void
                 for (int j2 = 0; j2 < 4; ++j2) {  // pairs (2 j2, 2 j2 + 1) of the 8 keys of this k-step
                     const float p0 = s[qt][2 * pr + (j2 >> 1)][2 * (j2 & 1)], p1 = s[qt][2 * pr + (j2 >> 1)][2 * (j2 & 1) + 1];
                     if constexpr (PLANES == 1) {
-                        h[j2] = pack2_bf16(p0, p1);
+                        h[j2] = bf16_pack2(p0, p1);
                     } else {
                         // p * 2048 <= 2048: no saturation clamp needed here
                         h[j2] = pack2_f16(p0, p1);
@@ -361,7 +339,7 @@ __global__ __launch_bounds__(RES ? 512 : 256, RES ? 1 : (NQT == 1 ? 4 : 2)) void
                         const int row = (2 * pr + t) * 16 + 4 * fh + tq;
                         const char* ap = sV + row * ROWB + ((u ^ vrow_swz(row)) << 5) + 8 * tp;
                         part2[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s16x4*)(uintptr_t)(unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)ap);
+                            (__attribute__((address_space(3))) s16x4*)(uintptr_t)lds_addr_of(ap));
                     }
                     s16x8 full = __builtin_shufflevector(part2[0], part2[1], 0, 1, 2, 3, 4, 5, 6, 7);
                     vf[pl] = *reinterpret_cast<uint4*>(&full);

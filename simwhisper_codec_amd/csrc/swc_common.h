@@ -42,10 +42,16 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float x) {
 // two f32 -> one dword (lo in bits 0..15, hi in 16..31), RNE: ONE v_cvt_pk_bf16_f32 (the `cast | cast << 16` form compiles
 // to one conversion per value plus the merge).  A vector conversion, not inline asm: hipcc then still inserts the wait
 // state a transcendental result needs before its first use.
-typedef float f32x2_c __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_c __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned bf16_pack2(float lo, float hi) {
-    const bf16x2_c r = __builtin_convertvector((f32x2_c){lo, hi}, bf16x2_c);
+    const bf16x2 r = __builtin_convertvector((f32x2){lo, hi}, bf16x2);
+    return *reinterpret_cast<const unsigned*>(&r);
+}
+// the same for two f16: ONE v_cvt_pk_f16_f32 (no saturation)
+__device__ __forceinline__ unsigned pack2_f16(float lo, float hi) {
+    const f16x2 r = __builtin_convertvector((f32x2){lo, hi}, f16x2);
     return *reinterpret_cast<const unsigned*>(&r);
 }
 __device__ __forceinline__ float bf16_to_f32(bf16_t x) {
@@ -75,14 +81,12 @@ __device__ __forceinline__ long f16s_col(long k) { return (k >> 5) * 64 + (k & 3
 // two values at once -> one dword of hi halves, one of lo halves: the conversions are the packed forms (one
 // v_cvt_pk_f16_f32 per pair, RNE like the scalar casts), the clamp one v_med3 each, the range tracking one v_max3 for both.
 // Bit-identical to two f16s_split calls.
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void f16s_split2(float a, float b, unsigned& hi2, unsigned& lo2, float& amax) {
     amax = fmaxf(fmaxf(amax, fabsf(a)), fabsf(b));
     a = __builtin_amdgcn_fmed3f(a, -SWC_F16S_LIMIT, SWC_F16S_LIMIT);
     b = __builtin_amdgcn_fmed3f(b, -SWC_F16S_LIMIT, SWC_F16S_LIMIT);
-    const f16x2_t h = __builtin_convertvector((f32x2_t){a, b}, f16x2_t);
-    const f16x2_t l = __builtin_convertvector((f32x2_t){a - (float)h[0], b - (float)h[1]}, f16x2_t);
+    const f16x2 h = __builtin_convertvector((f32x2){a, b}, f16x2);
+    const f16x2 l = __builtin_convertvector((f32x2){a - (float)h[0], b - (float)h[1]}, f16x2);
     hi2 = *reinterpret_cast<const unsigned*>(&h);
     lo2 = *reinterpret_cast<const unsigned*>(&l);
 }

@@ -18,15 +18,11 @@
 //   * epilogue: out^T through LDS (transposed, two passes of 64 frames) so that the residual stream is read and written
 //     in whole 2 KiB rows.
 //
-// MFMA: v_mfma_f32_32x32x16_bf16.  Operand maps (lane l): A[row l&31][k = 8(l>>5) + j], B[k = 8(l>>5) + j][col l&31],
-// D[row (r&3) + 8(r>>2) + 4(l>>5)][col l&31], r = 0..15.
+// MFMA: v_mfma_f32_32x32x16_bf16; operand maps in swc_mfma.h.
 #include <type_traits>
-#include "swc_common.h"
+#include "swc_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // one MFMA operand fragment (8 bf16) as a native vector: asm "v" operand
 
 constexpr int CX_C = 512;        // channels (K of GEMM1, N of GEMM2)
 constexpr int CX_BM = 128;       // frames per workgroup
@@ -59,24 +55,6 @@ constexpr int CX_TLD = CX_C + 4;  // row pitch (floats) of the epilogue transpos
 #define CX_RES_ACC 0
 #endif
 
-__device__ __forceinline__ void cx_glds16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    // one v_cvt_pk_bf16_f32 for the pair (RNE).  Only for operands that a plain VALU instruction produced (here: the fma
-    // that ends gelu_fast): hipcc does not insert, for an asm statement, the wait state that a transcendental result needs
-    // before its first use (swc_attention16 uses the vector-conversion form for that reason).
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 // F16 (operand_dtype SWC_F16): the block's internal operands — LayerNorm output, GELU output, both weight matrices — are IEEE
 // half precision instead of bf16: 11 significand bits instead of 8 at the same MFMA rate.  Their ranges are bounded by the block
 // itself (|LayerNorm output| <= sqrt(C) |ln_w| + |ln_b|; hidden activations of O(10); weights < 1), three to four orders of
@@ -84,19 +62,14 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 template <bool F16>
 __device__ __forceinline__ unsigned pack_x2(float lo, float hi) {
     if constexpr (F16) {
-        unsigned r;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-        return r;
+        return pack_f16x2(lo, hi);
     } else {
         return pack_bf16x2(lo, hi);
     }
 }
 
-// GEMM1's MFMAs in VGPR form.  The 256 accumulators of GEMM2 fill the AGPR half of the register file; left to hipcc, the
-// 64 accumulators of GEMM1 are also given AGPR-form MFMAs and the two sets are shuffled between the halves with ~1500
-// v_accvgpr_read/write/mov per slice (6 k issue cycles beside 8 k MFMA cycles).  Written as asm with "v" operands these
-// four MFMAs keep their accumulators in VGPRs, where the GELU reads them directly.  One statement per k-step: the
-// leading s_nop 1 covers a VALU copy of an operand hipcc may have placed right in front (it pads nothing inside asm).
+// GEMM1's MFMAs of one k-step in VGPR form: one hidden block x 4 frame blocks (why asm and not the builtin: see mfma32 in
+// swc_mfma.h)
 template <bool F16 = false>
 __device__ __forceinline__ void mfma32x4_vgpr(const u32x4& a, const u32x4& b0, const u32x4& b1, const u32x4& b2, const u32x4& b3,
                                               f32x16& c0, f32x16& c1, f32x16& c2, f32x16& c3) {
@@ -116,15 +89,6 @@ __device__ __forceinline__ void mfma32x4_vgpr(const u32x4& a, const u32x4& b0, c
             "v_mfma_f32_32x32x16_bf16 %3, %4, %8, %3"
             : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3)
             : "v"(a), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
-}
-
-template <bool F16 = false>
-__device__ __forceinline__ f32x16 mfma32(const u32x4& a, const u32x4& b, f32x16 c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(&a), *reinterpret_cast<const f16x8*>(&b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b),
-                                                       c, 0, 0, 0);
 }
 
 // front half of the block for the fused form: depthwise Conv1d(k7, pad 3, per utterance) + LayerNorm (modules.py:1233-1239)
@@ -171,14 +135,14 @@ __global__ __launch_bounds__(256, 1) void convnext_mlp_kernel(const bf16_t* __re
     // [(4 s + fb)][lane][16 B]; lane l supplies frame 32 fb + (l & 31), channels 16 s + 8 (l >> 5) .. + 7.  LDS-DMA with a
     // per-lane source address writes exactly this lane-linear image.
     if constexpr (!FUSED_DW) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+        const unsigned lds0 = lds_addr_of(smem);
 #pragma unroll 4
         for (int i = 0; i < 32; ++i) {
             const int frag = w * 32 + i;
             const int s = frag >> 2, fb = frag & 3;
             int row = row0 + 32 * fb + lf;
             row = row < M ? row : M - 1;  // rows beyond M are computed on a copy of the last row and never stored
-            cx_glds16(y + (long)row * CX_C + 16 * s + 8 * lh, lds0 + frag * 1024);
+            glds16(y + (long)row * CX_C + 16 * s + 8 * lh, lds0 + frag * 1024);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -625,14 +589,14 @@ __global__ __launch_bounds__(256, 1) void convnext16_kernel(const bf16_t* __rest
     // [(8 s + fb)][lane][16 B]; lane l supplies frame 16 fb + (l & 15), channels 32 s + 8 (l >> 4) .. + 7.  LDS-DMA with a
     // per-lane source address writes exactly this lane-linear image.
     if constexpr (!FUSED_DW) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+        const unsigned lds0 = lds_addr_of(smem);
 #pragma unroll 4
         for (int i = 0; i < 32; ++i) {
             const int frag = w * 32 + i;
             const int s = frag >> 3, fb = frag & 7;
             int row = row0 + 16 * fb + lf;
             row = row < M ? row : M - 1;  // rows beyond M are computed on a copy of the last row and never stored
-            cx_glds16(y + (long)row * CX_C + 32 * s + 8 * lh, lds0 + frag * 1024);
+            glds16(y + (long)row * CX_C + 32 * s + 8 * lh, lds0 + frag * 1024);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();

@@ -5,17 +5,14 @@
 // workgroup owns 64 frames: 128 accumulator registers (AGPRs) + 128 VGPRs per wave, 80 KiB of LDS (y tile 64 KiB + H exchange
 // 16 KiB), so two workgroups share a CU (2 waves per SIMD: one's stalls are the other's issue slots) and the second one can be
 // started late (`stagger_cycles`) so that its HBM phases fall into the first one's slice loop.  The price is the weight stream:
-// every 1 KiB fragment feeds two MFMAs instead of four.  Structure and operand maps as in swc_convnext.hip / swc_mlp.hip:
+// every 1 KiB fragment feeds two MFMAs instead of four.  Structure as in swc_convnext.hip / swc_mlp.hip (operand maps: swc_mfma.h):
 //   slice j of 128 hidden values: GEMM1 wave w: H^T[32 hidden][64 frames] = W1 . y^T (K = 512, 32 k-steps x 2 MFMAs, VGPR-form asm);
 //   GELU on the accumulators, converted in place to bf16 B fragments, exchanged through LDS; GEMM2 wave w: out^T[128 columns]
 //   [64 frames] += W2 . H^T (8 k-steps x 8 MFMAs, 128 AGPRs); weights global -> VGPR from a per-wave stream (8 fragments in flight).
 #include <type_traits>
-#include "swc_common.h"
+#include "swc_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C6_C = 512;
 constexpr int C6_BM = 64;
@@ -31,33 +28,12 @@ constexpr int C6_LDS = C6_Y_BYTES + C6_H_BYTES;  // 80 KiB: two workgroups per C
 constexpr int C6_TLD = C6_C + 4;
 static_assert(32 * C6_TLD * 4 <= C6_LDS, "epilogue buffer");
 
-__device__ __forceinline__ void c6_glds16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
-
-__device__ __forceinline__ unsigned c6_pack_bf16x2(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 __device__ __forceinline__ void c6_mfma1x2_vgpr(const u32x4& a, const u32x4& b0, const u32x4& b1, f32x16& c0, f32x16& c1) {
     asm("s_nop 1\n\t"
         "v_mfma_f32_32x32x16_bf16 %0, %2, %3, %0\n\t"
         "v_mfma_f32_32x32x16_bf16 %1, %2, %4, %1"
         : "+v"(c0), "+v"(c1)
         : "v"(a), "v"(b0), "v"(b1));
-}
-
-__device__ __forceinline__ f32x16 c6_mfma32(const u32x4& a, const u32x4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b),
-                                                   c, 0, 0, 0);
 }
 
 // wstream: per wave w (4 of them) NS * 64 + C6_PF fragments of 1 KiB in the order of consumption (convnext64_pack_kernel)
@@ -80,14 +56,14 @@ __global__ __launch_bounds__(256, 2) void convnext64_kernel(const bf16_t* __rest
 
     // ---- y tile -> LDS as B fragments by DMA: fragment (s, fb) at [(2 s + fb)][lane][16 B]
     {
-        const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+        const unsigned lds0 = lds_addr_of(smem);
 #pragma unroll 4
         for (int i = 0; i < 16; ++i) {
             const int frag = w * 16 + i;
             const int s = frag >> 1, fb = frag & 1;
             int row = row0 + 32 * fb + lf;
             row = row < M ? row : M - 1;
-            c6_glds16(y + (long)row * C6_C + 16 * s + 8 * lh, lds0 + frag * 1024);
+            glds16(y + (long)row * C6_C + 16 * s + 8 * lh, lds0 + frag * 1024);
         }
     }
     const u32x4* ylds = reinterpret_cast<const u32x4*>(smem) + lane;
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void convnext64_kernel(const bf16_t* __rest
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = gelu_fast(acc1[b][8 * t + 4 * h + e]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc1[b][4 * t + 2 * h + i] = __uint_as_float(c6_pack_bf16x2(v[2 * i], v[2 * i + 1]));
+        for (int i = 0; i < 2; ++i) acc1[b][4 * t + 2 * h + i] = __uint_as_float(pack_bf16x2(v[2 * i], v[2 * i + 1]));
     };
     auto store_h = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -178,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void convnext64_kernel(const bf16_t* __rest
 #pragma unroll
             for (int n = 0; n < C6_NB; ++n) {
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc2[n][b] = c6_mfma32(ring[(q * C6_NB + n) % C6_PF], cur[b], acc2[n][b]);
+                for (int b = 0; b < 2; ++b) acc2[n][b] = mfma32(ring[(q * C6_NB + n) % C6_PF], cur[b], acc2[n][b]);
                 ring[(q * C6_NB + n) % C6_PF] = wfrag(q * C6_NB + n + C6_PF);
             }
             if constexpr (decltype(with_gelu)::value) gelu_half(q >> 2, (q >> 1) & 1, q & 1);

@@ -5,7 +5,7 @@
 //   128 x 128 tile, 4 waves (2x2, MT=4), 64 KiB LDS, 2 workgroups / CU   — f32 and bf16, any shape
 //   256 x 256 tile, 8 waves (2x4, MT=8), 128 KiB LDS, 1 workgroup / CU   — bf16, large M and N
 // K is walked in 128-byte slices (32 f32 / 64 bf16) through a double-buffered LDS image filled by
-// LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write).
+// LDS-DMA (glds16 / glds16_s in swc_mfma.h: no VGPR round trip, no ds_write).
 //
 // f32 : v_mfma_f32_16x16x4_f32   (bit-for-bit an f32 fma chain: the parity path)
 // bf16: v_mfma_f32_16x16x32_bf16 (f32 accumulate)
@@ -19,7 +19,7 @@
 // The product is computed TRANSPOSED (weight fragment = MFMA row operand) with the weight rows of a
 // fragment taken as {16a + 4j + b}: lane (fr, fh) then owns, for activation row 16i + fr, the 16
 // CONTIGUOUS output columns 16fh + 4j + e — 64-byte vector stores, full lines per row across fh.
-#include "swc_common.h"
+#include "swc_mfma.h"
 
 // Geometry overrides for A/B measurements exist only in tuning builds (-DSWC_TUNING, tools/build_variant.sh): the
 // shipped library reads no environment variable and keeps no mutable process-wide state.
@@ -41,34 +41,6 @@ __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 
 __device__ unsigned long long g_stamps[512 * 8 * 8];  // [workgroup][wave][compute, vmcnt wait, barrier wait, slices, epilogue, tiles, tail, -]
 #endif
 
-// 16 bytes per lane, global -> LDS (global_load_lds_dwordx4).  `lds_addr` is the wave-uniform LDS byte
-// address; lane l lands at lds_addr + 16 l.  Written as inline asm on purpose: hipcc drains a
-// compiler-visible LDS-DMA (s_waitcnt vmcnt(0)) in front of the next ds_read, which would serialise the
-// prefetch of slice t+1 with the MFMAs of slice t.  Hidden in asm, the DMA is ordered by our own
-// `s_waitcnt vmcnt(N)` + barrier (cdna_hip_programming.md 5.7).  M0 is saved/restored inside the statement.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);  // wave-uniform by construction; pin it to an SGPR
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
-// same, address = wave-uniform 64-bit base (SGPR pair) + per-lane unsigned 32-bit byte offset: one VGPR per lane
-// instead of a 64-bit pointer per staged row
-__device__ __forceinline__ void glds16_s(const char* base, unsigned off, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(off), "s"(base), "s"(lds_addr)
-        : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 
 // conflict-free for the four 16-lane groups of ds_read_b128, both for 16 consecutive rows (activation
 // fragments) and for the permuted weight rows {16a + 4j + b} (checked exhaustively)
@@ -110,8 +82,6 @@ constexpr int EPI_WAVE_BYTES = 16 * EPI_TP * 4;  // 16 rows x 64 columns per wav
 // Epilogue stores.  Tuning builds can change how they are issued (tools/build_variant.sh):
 //   -DSWC_ABL_NOSTORE   timing ablation only, WRONG RESULTS: the values are computed and kept live, nothing is stored —
 //                       what a launch would cost if its epilogue stores were free
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 // `nt` (wave-uniform): non-temporal store — the line is not kept dirty in the XCD's L2 (see GemmP::nt_mode)
 __device__ __forceinline__ void epi_st128(void* p, unsigned a, unsigned b, unsigned c, unsigned d, bool nt = false) {
 #if defined(SWC_ABL_NOSTORE)
@@ -120,7 +90,7 @@ __device__ __forceinline__ void epi_st128(void* p, unsigned a, unsigned b, unsig
     (void)nt;
     *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 #else
-    if (nt) __builtin_nontemporal_store((u32x4_t){a, b, c, d}, reinterpret_cast<u32x4_t*>(p));
+    if (nt) __builtin_nontemporal_store((u32x4){a, b, c, d}, reinterpret_cast<u32x4*>(p));
     else *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 #endif
 }
@@ -134,7 +104,7 @@ __device__ __forceinline__ void epi_st64(void* p, unsigned a, unsigned b, bool n
     (void)nt;
     *reinterpret_cast<uint2*>(p) = make_uint2(a, b);
 #else
-    if (nt) __builtin_nontemporal_store((u32x2_t){a, b}, reinterpret_cast<u32x2_t*>(p));
+    if (nt) __builtin_nontemporal_store((u32x2){a, b}, reinterpret_cast<u32x2*>(p));
     else *reinterpret_cast<uint2*>(p) = make_uint2(a, b);
 #endif
 }

@@ -30,15 +30,11 @@
 // template F8, preset fp8_fc1 — with fc1 on the block-scaled fp8 MFMA.  Measured: 181 us (bf16) / 152 us (fp8 fc1)
 // per layer at 16 000 tokens against 238 us for the five launches of round 3.
 //
-// MFMA: v_mfma_f32_32x32x16_bf16.  Operand maps (lane l): A[row l&31][k = 8(l>>5) + j], B[k = 8(l>>5) + j][col l&31],
-// D[row (r&3) + 8(r>>2) + 4(l>>5)][col l&31], r = 0..15.
+// MFMA: v_mfma_f32_32x32x16_bf16; operand maps in swc_mfma.h.
 #include <type_traits>
-#include "swc_common.h"
+#include "swc_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ML_D = 768;         // model width (K of GEMM1, N of GEMM2)
 constexpr int ML_BM = 64;         // tokens per workgroup
@@ -68,15 +64,8 @@ static_assert(32 * ML_TLD * 4 <= ML_LDS, "epilogue buffer");
 #define ML_ABL 0
 #endif
 
-__device__ __forceinline__ unsigned ml_pack_bf16x2(float lo, float hi) {
-    // one v_cvt_pk_bf16_f32 (RNE); only for operands a plain VALU instruction produced (see swc_convnext.hip)
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
-// GEMM1's MFMAs of one k-step in VGPR form: 2 hidden blocks x 2 token blocks (see mfma32x4_vgpr in swc_convnext.hip for why
-// these are asm: left to hipcc both accumulator sets get AGPR-form MFMAs and are shuffled between the register halves)
+// GEMM1's MFMAs of one k-step in VGPR form: 2 hidden blocks x 2 token blocks (why asm and not the builtin: see mfma32 in
+// swc_mfma.h)
 template <bool F16 = false>
 __device__ __forceinline__ void ml_mfma2x2_vgpr(const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1,
                                                 f32x16& c00, f32x16& c01, f32x16& c10, f32x16& c11) {
@@ -112,15 +101,6 @@ __device__ __forceinline__ void ml_mfma8_1x4_vgpr(const i32x8& a, const i32x8& b
         : "v"(a), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(sc));
 }
 
-template <bool F16 = false>
-__device__ __forceinline__ f32x16 ml_mfma32(const u32x4& a, const u32x4& b, f32x16 c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(&a), *reinterpret_cast<const f16x8*>(&b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b),
-                                                       c, 0, 0, 0);
-}
-
 // F16 (operand_dtype SWC_F16, with OPROJ): every MFMA operand INSIDE the kernel — the attention tile (converted in LDS: bf16 -> f16 is
 // exact), LayerNorm(x'), GELU(h) and the three weight matrices of the stream — is IEEE half precision instead of bf16: 11
 // significand bits instead of 8 at the same MFMA rate.  f16 has a finite range where bf16 has f32's: conversions saturate at
@@ -130,11 +110,9 @@ __device__ __forceinline__ unsigned ml_pack_x2(float lo, float hi) {
     if constexpr (F16) {
         lo = __builtin_amdgcn_fmed3f(lo, -65504.0f, 65504.0f);
         hi = __builtin_amdgcn_fmed3f(hi, -65504.0f, 65504.0f);
-        unsigned r;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-        return r;
+        return pack_f16x2(lo, hi);
     } else {
-        return ml_pack_bf16x2(lo, hi);
+        return pack_bf16x2(lo, hi);
     }
 }
 
@@ -142,17 +120,6 @@ struct MlNorm {
     const float* w;  // [D]
     const float* b;  // [D]
 };
-
-__device__ __forceinline__ void ml_glds16(const void* gsrc, unsigned lds_addr) {
-    // one LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS at lds_addr (wave-uniform)
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
 
 constexpr int ML_P0 = ML_KS1 * ML_NB;  // fragments per wave of the out-proj phase (OPROJ): 48 k-steps x 6 column blocks
 static_assert(ML_P0 % ML_PF == 0, "the ring index of a fragment must not depend on the phase");
@@ -282,14 +249,14 @@ __global__ __launch_bounds__(256, 1) void mlp_block_kernel(const float* x, float
     } else {
         // ---- OPROJ prologue.  (1) attention tile -> LDS as B fragments by DMA: fragment (s, fb) = k-step s (16 channels) x
         // token block fb at [(2 s + fb) * ML_YP]; lane l supplies token 32 fb + (l & 31), channels 16 s + 8 (l >> 5) .. + 7
-        const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+        const unsigned lds0 = lds_addr_of(smem);
 #pragma unroll 4
         for (int i = 0; i < 2 * ML_KS1 / 4; ++i) {
             const int frag = w * (2 * ML_KS1 / 4) + i;
             const int s_ = frag >> 1, fb = frag & 1;
             int row = row0 + 32 * fb + lf;
             row = row < M ? row : M - 1;  // rows beyond M are computed on a copy of the last row and never stored
-            ml_glds16(att + (long)row * ML_D + 16 * s_ + 8 * lh, lds0 + frag * ML_YP);
+            glds16(att + (long)row * ML_D + 16 * s_ + 8 * lh, lds0 + frag * ML_YP);
         }
         // (2) the accumulators start at the residual stream + out-proj bias, in the accumulator layout: register r = 4 g + e
         // of tile (n, fb) in lane (lf, lh) is token 32 fb + lf, column 192 w + 32 n + 8 g + 4 lh + e
@@ -338,7 +305,7 @@ __global__ __launch_bounds__(256, 1) void mlp_block_kernel(const float* x, float
 #pragma unroll
                 for (int n = 0; n < ML_NB; ++n) {
 #pragma unroll
-                    for (int b = 0; b < 2; ++b) acc2[n][b] = ml_mfma32<F16>(ring[(s_ * ML_NB + n) % ML_PF], cur[b], acc2[n][b]);
+                    for (int b = 0; b < 2; ++b) acc2[n][b] = mfma32<F16>(ring[(s_ * ML_NB + n) % ML_PF], cur[b], acc2[n][b]);
                     ring[(s_ * ML_NB + n) % ML_PF] = wfrag(s_ * ML_NB + n + ML_PF);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -594,7 +561,7 @@ __global__ __launch_bounds__(256, 1) void mlp_block_kernel(const float* x, float
 #pragma unroll
             for (int n = 0; n < ML_NB; ++n) {
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc2[n][b] = ml_mfma32<F16>(ring[(q * ML_NB + n) % ML_PF], cur[b], acc2[n][b]);
+                for (int b = 0; b < 2; ++b) acc2[n][b] = mfma32<F16>(ring[(q * ML_NB + n) % ML_PF], cur[b], acc2[n][b]);
                 ring[(q * ML_NB + n) % ML_PF] = wfrag(q * ML_NB + n + ML_PF);
             }
             if constexpr (decltype(with_gelu)::value) {

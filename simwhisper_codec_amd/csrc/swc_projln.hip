@@ -22,14 +22,10 @@
 // rows; element arithmetic and order are those of swc_gemm's epilogue (acc * alpha + bias, + residual) and of swc_layernorm (row
 // sums on the DPP path, two-pass variance), so LayerNorm(x_out) is bit-identical to swc_layernorm on the row this kernel stored.
 //
-// MFMA: v_mfma_f32_32x32x16_f16.  Operand maps (lane l): A[row l&31][k = 8(l>>5) + j], B[k = 8(l>>5) + j][col l&31],
-// D[row (r&3) + 8(r>>2) + 4(l>>5)][col l&31], r = 0..15.
-#include "swc_common.h"
+// MFMA: v_mfma_f32_32x32x16_f16; operand maps in swc_mfma.h.
+#include "swc_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PL_N = 768;          // output columns = width of the residual stream
 constexpr int PL_BM = 64;          // tokens per workgroup
@@ -55,21 +51,6 @@ struct PlNorm {
     const float* b;  // [768]
 };
 
-__device__ __forceinline__ f32x16 pl_mfma(const u32x4& a, const u32x4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(&a), *reinterpret_cast<const f16x8*>(&b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void pl_glds16(const void* gsrc, unsigned lds_addr) {
-    // one LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS at lds_addr (wave-uniform)
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_addr)
-        : "memory");
-}
-
 // wstream: per wave w (4 of them) (K / 16) * 12 + PL_PF fragments of 1 KiB in the order of consumption (projln_pack_kernel)
 __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__ a, long a_pitch /* bytes per row of A */,
                                                         const u32x4* __restrict__ wstream, const float* __restrict__ bias,
@@ -83,19 +64,13 @@ __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__
     const int row0 = blockIdx.x * PL_BM;
     const int NST = K / PL_KST;
 
-    const long per_wave = (long)(K / 16) * 2 * PL_NB + PL_PF;  // fragments
-    const char* wbase = reinterpret_cast<const char*>(wstream) + (long)w * per_wave * 1024;
-    const unsigned lane_off = (unsigned)lane * 16u;
-    auto wfrag = [&](int i) __attribute__((always_inline)) -> u32x4 {  // fragment i of the current stage (i may run PL_PF past its end)
-        if (PL_ABL & 4) i &= PL_PF - 1;
-        return *reinterpret_cast<const u32x4*>(wbase + (long)i * 1024 + lane_off);
-    };
+    WeightStream<PL_PF, PL_ABL> ws(wstream, w, (long)(K / 16) * 2 * PL_NB + PL_PF, lane);
     u32x4 ring[PL_PF];
 
     // ---- A staging: stage t = k 64 t .. 64 t + 63 as 16 fragments [k-step ks (4)][plane: hi, lo][token block fb (2)] of 1 KiB.
     // Wave w issues the 4 fragments of k-step ks = w: lane l supplies token 32 fb + (l & 31), k = 16 ks + 8 (l >> 5) .. + 7 — in the
     // split row that is 16 bytes at [32-block (2 t + ks / 2)] * 128 + plane * 64 + (ks & 1) * 32 + (l >> 5) * 16
-    const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+    const unsigned lds0 = lds_addr_of(smem);
     const char* arow[2];
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb) {
@@ -108,7 +83,7 @@ __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__
 #pragma unroll
         for (int plane = 0; plane < 2; ++plane)
 #pragma unroll
-            for (int fb = 0; fb < 2; ++fb) pl_glds16(arow[fb] + (long)t * 256 + plane * 64, dst + (plane * 2 + fb) * 1024);
+            for (int fb = 0; fb < 2; ++fb) glds16(arow[fb] + (long)t * 256 + plane * 64, dst + (plane * 2 + fb) * 1024);
     };
     const u32x4* alds = reinterpret_cast<const u32x4*>(smem) + lane;
     auto a_frags = [&](int t, int ks, u32x4 (&xh)[2], u32x4 (&xl)[2]) __attribute__((always_inline)) {
@@ -134,7 +109,7 @@ __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__
     // entries; with the preload in any other order than the loop's own refills it drained the whole ring once per stage
 #pragma unroll
     for (int i = 0; i < PL_PF; ++i) {
-        ring[i] = wfrag(i);
+        ring[i] = ws.frag(i);
         __builtin_amdgcn_sched_barrier(0);
     }
 
@@ -146,21 +121,21 @@ __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__
         for (int n = 0; n < PL_NB; ++n) {
             const int sl = (i0 + n) % PL_PF;
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[n][b] = pl_mfma(ring[sl], xh[b], acc[n][b]);  // W_lo . x_hi
-            ring[sl] = wfrag(i0 + n + PL_PF);
+            for (int b = 0; b < 2; ++b) acc[n][b] = mfma32<true>(ring[sl], xh[b], acc[n][b]);  // W_lo . x_hi
+            ring[sl] = ws.frag(i0 + n + PL_PF);
         }
 #pragma unroll
         for (int n = 0; n < PL_NB; ++n) {
             const int sl = (i0 + PL_NB + n) % PL_PF;
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[n][b] = pl_mfma(ring[sl], xl[b], acc[n][b]);  // W_hi . x_lo
+            for (int b = 0; b < 2; ++b) acc[n][b] = mfma32<true>(ring[sl], xl[b], acc[n][b]);  // W_hi . x_lo
         }
 #pragma unroll
         for (int n = 0; n < PL_NB; ++n) {
             const int sl = (i0 + PL_NB + n) % PL_PF;
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[n][b] = pl_mfma(ring[sl], xh[b], acc[n][b]);  // W_hi . x_hi
-            ring[sl] = wfrag(i0 + PL_NB + n + PL_PF);
+            for (int b = 0; b < 2; ++b) acc[n][b] = mfma32<true>(ring[sl], xh[b], acc[n][b]);  // W_hi . x_hi
+            ring[sl] = ws.frag(i0 + PL_NB + n + PL_PF);
         }
     };
 
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void projln_kernel(const char* __restrict__
         __builtin_amdgcn_sched_barrier(0);
         kstep(36, hB, lB);
         __builtin_amdgcn_sched_barrier(0);
-        wbase += PL_FPS * 1024;
+        ws.base += PL_FPS * 1024;
     }
     __syncthreads();  // LDS is free: the epilogue re-uses it
 
