@@ -11,6 +11,11 @@ file loading for batch i+1 and saving of batch i-1 overlap the GPU work of batch
 batches on the GPU at a time (two streams over one set of weights: same files, more throughput), and
 `--precision` / `--synthetic_checkpoint` exist because the trained weights cannot be fetched offline.
 
+`--mode encode` writes the compressed codes instead, `<output_dir>/<basename>.swc` (the SWC1 format of
+simwhisper_codec_amd/bitstream.py: 11 bytes per 80 ms frame, 10 s of audio = 1 387 bytes), and `--mode decode` turns every
+`*.swc` under --input_dir back into `<output_dir>/<basename>.wav`.  With the same file names and --batch_size the two runs
+write the WAV files of one `--mode roundtrip` (the default) run.  Both are single-GPU modes.
+
 Several GPUs of one node (BASELINE.json configs[3]): launch the same command under torch.distributed.run
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 inference.py ... --batch_size 32
@@ -33,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from audiocodec.model import AudioCodec  # noqa: E402
+from simwhisper_codec_amd import bitstream  # noqa: E402
 from simwhisper_codec_amd.pipeline import HostStager  # noqa: E402
 from simwhisper_codec_amd.wavio import find_audio_files, load_audio, read_pcm, read_pcm16, save_audio, save_pcm16  # noqa: E402
 
@@ -45,6 +51,9 @@ def set_logging(level="INFO"):
 
 def build_parser():
     p = argparse.ArgumentParser()
+    p.add_argument("--mode", type=str, default="roundtrip", choices=["roundtrip", "encode", "decode"],
+                   help="roundtrip (default): audio files -> <basename>.wav, the reference's CLI.  encode: audio files -> "
+                        "<basename>.swc, the packed codes (1100 bit/s).  decode: the *.swc files of --input_dir -> <basename>.wav")
     p.add_argument("--config_path", type=str, default="./config/SimWhisperCodec.yaml")
     p.add_argument("--checkpoint_path", type=str, default="./weights/SimWhisperCodec.pt")
     p.add_argument("--device", type=str, default="cuda")
@@ -120,10 +129,18 @@ def main(argv=None):
     set_logging()
     args = build_parser().parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", 1))
+    if world > 1 and args.mode != "roundtrip":
+        raise SystemExit(f"--mode {args.mode} runs on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
+                         "only --mode roundtrip is data-parallel")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    if args.mode != "roundtrip" and device.type != "cuda":
+        raise SystemExit(f"--mode {args.mode} packs and unpacks the codes on the GPU: --device must be a CUDA device")
     generator = load_model(args, device)
+    if args.mode == "decode":
+        return main_decode(args, generator, device)
+    to_codes = args.mode == "encode"
     audio_paths = find_audio_files(input_dir=args.input_dir)
     os.makedirs(args.output_dir, exist_ok=True)
     logging.info(f"Processing {len(audio_paths)} audio files, output will be saved to {args.output_dir}")
@@ -146,6 +163,11 @@ def main(argv=None):
             save_pcm16(out, wav, sample_rate=generator.output_sample_rate)
         else:
             save_audio(out, wav.reshape(1, -1), sample_rate=generator.output_sample_rate)
+
+    def save_image(item):
+        path, image = item
+        with open(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ".swc"), "wb") as f:
+            f.write(image.numpy())
 
     def stage_in(cpu_wavs):
         if not on_gpu:
@@ -171,8 +193,11 @@ def main(argv=None):
 
     def save(paths, wavs):
         t = time.perf_counter()
-        host = stager.to_host(wavs) if on_gpu else wavs        # (the batch's stream was synchronised before it was handed back)
-        list(io.map(save_one, zip(paths, host)))
+        if to_codes:   # wavs = bitstream.pack_batch's result: one copy into pinned memory, every file a slice of it
+            list(io.map(save_image, zip(paths, bitstream.images_to_host(wavs))))
+        else:
+            host = stager.to_host(wavs) if on_gpu else wavs    # (the batch's stream was synchronised before it was handed back)
+            list(io.map(save_one, zip(paths, host)))
         account("d2h+save", time.perf_counter() - t)
 
     def process(model, item):
@@ -182,6 +207,9 @@ def main(argv=None):
             t1 = time.perf_counter()
             def round_trip():
                 codes = model.encode(wav_list, overlap_seconds=10, device=device)["codes_list"]
+                if to_codes:   # the file images of the batch, packed on the device by one launch (inside the range check)
+                    with torch.cuda.device(device):
+                        return codes, bitstream.pack_batch(codes)
                 return codes, model.decode(codes, overlap_seconds=10, device=device)["syn_wav_list"]
             # the range check of the split-f16 encoder is read from a snapshot behind the encode kernels once the decode has been
             # enqueued (no stall between the two calls); a clipped batch is redone on exact-f32 operands
@@ -193,7 +221,7 @@ def main(argv=None):
                     codes_list, syn = round_trip()
                 if chk.clipped:
                     codes_list, syn = round_trip()
-            out = stager.pcm16_on_device(syn) if on_gpu else [w.cpu() for w in syn]
+            out = syn if to_codes else (stager.pcm16_on_device(syn) if on_gpu else [w.cpu() for w in syn])
             if on_gpu:
                 torch.cuda.current_stream().synchronize()
             account("encode+decode", time.perf_counter() - t1)
@@ -212,8 +240,12 @@ def main(argv=None):
             nonlocal total_audio, pending_save
             paths, clens, host = fut.result() if hasattr(fut, "result") else fut
             logging.info(f"Encoding completed, code lengths: {clens}")
-            logging.info(f"Decoding completed, generated waveform lengths: {[len(w) for w in host]} samples")
-            total_audio += sum(len(w) for w in host) / generator.output_sample_rate
+            if to_codes:
+                logging.info(f"Packing completed, code file sizes: {host[2]} bytes")
+                total_audio += sum(clens) * generator.encoder_downsample_rate / generator.input_sample_rate
+            else:
+                logging.info(f"Decoding completed, generated waveform lengths: {[len(w) for w in host]} samples")
+                total_audio += sum(len(w) for w in host) / generator.output_sample_rate
             if pending_save is not None:
                 pending_save.result()
             pending_save = pool.submit(save, paths, host)
@@ -240,6 +272,75 @@ def main(argv=None):
     logging.info(f"All audio processing completed: {total_audio:.1f} s of audio in {dt:.2f} s "
                  f"({total_audio / max(dt, 1e-9):.1f} x real time incl. file IO)")
     logging.info("stage wall seconds (overlapping threads): " + ", ".join(f"{k} {v:.2f}" for k, v in spent.items()))
+
+
+def find_code_files(input_dir):
+    """the *.swc files under input_dir, in the order wavio.find_audio_files gives audio files (recursive, sorted by path)"""
+    import glob
+    return sorted(glob.glob(os.path.join(input_dir, "**", "*.swc"), recursive=True))
+
+
+def main_decode(args, generator, device):
+    """--mode decode: every *.swc of --input_dir -> <output_dir>/<basename>.wav (PCM16), --batch_size files per decode() call.
+    Per batch: the files are read by the io threads and their headers checked on the host, their payloads cross PCIe as one
+    copy and are unpacked by one launch, and nothing is decoded or written before every file of the batch has been found
+    sound (a file that cannot be read, a bad header, a cut payload or code values outside the model's codebook stop the run
+    with the file's name).  Reading batch i+1 and writing batch i-1 overlap the GPU work of batch i."""
+    import math
+    paths_all = find_code_files(args.input_dir)
+    os.makedirs(args.output_dir, exist_ok=True)
+    logging.info(f"Decoding {len(paths_all)} code files, output will be saved to {args.output_dir}")
+    bs = args.batch_size
+    batches = [paths_all[i:i + bs] for i in range(0, len(paths_all), bs)]
+    n_codes = math.prod(generator.fsq_levels)
+    stager = HostStager()
+
+    def read_one(path):
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+        except OSError as e:
+            raise ValueError(f"{path}: cannot be read ({e})") from e
+        bitstream.parse_header(data, path)
+        return data
+
+    def save_one(item):
+        path, pcm = item
+        save_pcm16(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav"), pcm,
+                   sample_rate=generator.output_sample_rate)
+
+    total_audio, t0 = 0.0, time.perf_counter()
+    with ThreadPoolExecutor(max_workers=max(1, args.io_threads)) as io, ThreadPoolExecutor(max_workers=2) as pool, torch.no_grad():
+        def load(paths):
+            return list(io.map(read_one, paths))
+
+        def save(paths, host):
+            list(io.map(save_one, zip(paths, host)))
+
+        nxt = pool.submit(load, batches[0]) if batches else None
+        pending = None
+        for bi, paths in enumerate(batches):
+            logging.info(f"Processing batch {bi + 1}/{len(batches)}, files: {paths}")
+            blobs = nxt.result()
+            nxt = pool.submit(load, batches[bi + 1]) if bi + 1 < len(batches) else None
+            with torch.cuda.device(device):
+                _, views, wrong = bitstream.read_images(blobs, paths, device, n_codes=n_codes)
+                if wrong:
+                    raise ValueError(f"{', '.join(paths[i] for i in wrong)}: code values outside the codebook of {n_codes} entries "
+                                     "(a corrupt file, or codes of another model)")
+                logging.info(f"Successfully loaded {len(views)} code files with lengths {[v.shape[-1] for v in views]} frames")
+                syn = generator.decode(views, overlap_seconds=10, device=device)["syn_wav_list"]
+                host = stager.to_host(stager.pcm16_on_device(syn))
+            logging.info(f"Decoding completed, generated waveform lengths: {[len(w) for w in host]} samples")
+            total_audio += sum(len(w) for w in host) / generator.output_sample_rate
+            if pending is not None:
+                pending.result()
+            pending = pool.submit(save, paths, host)
+        if pending is not None:
+            pending.result()
+    dt = time.perf_counter() - t0
+    logging.info(f"All code files decoded: {total_audio:.1f} s of audio in {dt:.2f} s "
+                 f"({total_audio / max(dt, 1e-9):.1f} x real time incl. file IO)")
 
 
 def main_distributed(args, world):

@@ -95,6 +95,13 @@ AUDIO_SIGNATURES = {
     "swc_resample": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _L, _I, _P], C.c_int),
 }
 
+# include/swc_codes.h (batched code files), one to one: name -> (argtypes, restype).  Again a table of its own
+CODES_SIGNATURES = {
+    "swc_codefile_bytes": ([_L], C.c_int64),
+    "swc_codes_pack_batch": ([_P, _P, _P, _P, _I, _P, _L, _I, _I, _P], C.c_int),
+    "swc_codes_unpack_batch": ([_P, _L, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -116,7 +123,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in AUDIO_SIGNATURES.items():
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -4,11 +4,15 @@ codec: 8 x 11 bits = 11 bytes per 12.5 Hz frame = 1100 bit/s.
 
 File layout (little endian):  b"SWC1" | u32 n_frames | u8 n_groups (8) | u8 bits (11) | u16 reserved |
                               11 * n_frames payload bytes (frame-major, group g at bits 11g..11g+10, LSB first).
-Packing / unpacking run on the device (swc_codes_pack / swc_codes_unpack).
+Packing / unpacking run on the device (swc_codes_pack / swc_codes_unpack for one utterance; swc_codes_pack_batch /
+swc_codes_unpack_batch of include/swc_codes.h for a ragged batch: one launch and one host <-> device copy per batch).
+A concatenation of file images is itself parseable front to back (parse_header at the running offset).
 """
 import ctypes as C
 import struct
+import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -16,6 +20,8 @@ from .ops import _ptr, _stream
 
 MAGIC = b"SWC1"
 GROUPS, BITS, FRAME_BYTES = 8, 11, 11
+HEADER_BYTES = 12
+MAX_BATCH, MAX_FRAMES = 65535, 1 << 24   # limits of one batched call (include/swc_codes.h)
 
 
 def pack_codes(codes):
@@ -60,3 +66,223 @@ def read_codes(path, device="cuda"):
         raise ValueError(f"{path}: unsupported or truncated code file")
     payload = torch.frombuffer(bytearray(data[12:12 + FRAME_BYTES * n]), dtype=torch.uint8).to(device)
     return unpack_codes(payload, n)
+
+
+# ------------------------------------------------------------------ ragged batches (include/swc_codes.h)
+def image_bytes(n_frames):
+    """12 + 11 n_frames: the size of one SWC1 file image (swc_codefile_bytes)"""
+    return HEADER_BYTES + FRAME_BYTES * int(n_frames)
+
+
+def header(n_frames):
+    return MAGIC + struct.pack("<IBBH", int(n_frames), GROUPS, BITS, 0)
+
+
+def parse_header(data, name="<bytes>", offset=0):
+    """The image that starts at data[offset] -> its n_frames; its payload is data[offset + 12 : offset + 12 + 11 n_frames].
+    Raises ValueError naming `name` for a wrong magic, an unsupported group count or code width, and a payload cut short.
+    Bytes behind the image are not looked at, so a concatenation of images is walked by moving `offset` on."""
+    have = len(data) - offset
+    if have < HEADER_BYTES or bytes(data[offset:offset + 4]) != MAGIC:
+        raise ValueError(f"{name}: not a SWC1 code file")
+    n, g, b, _ = struct.unpack_from("<IBBH", data, offset + 4)
+    if g != GROUPS or b != BITS:
+        raise ValueError(f"{name}: unsupported code file ({g} groups of {b} bits; this container holds {GROUPS} x {BITS})")
+    if have < HEADER_BYTES + FRAME_BYTES * n:
+        raise ValueError(f"{name}: truncated code file ({have} bytes, its header announces {n} frames = {image_bytes(n)} bytes)")
+    return n
+
+
+def _meta(values, device):
+    """host int lists -> one int64 device tensor (one small upload per launch, as ops.resample does)"""
+    return torch.tensor(values, dtype=torch.int64).to(device, non_blocking=True)
+
+
+def pack_batch(codes_list, offsets=None, out=None):
+    """B utterances -> their B complete file images inside ONE device uint8 buffer, in one launch (swc_codes_pack_batch).
+    codes_list: device tensors (8, T_b), int32 or int64, unit column stride (encode()'s strided views are taken as they are).
+    offsets: where image b starts in the buffer (default: back to back, so the buffer is the concatenation of the files);
+    out: the uint8 device buffer to write into (default: a new one that ends with the last image).  Only the images are
+    written.  -> (buffer, offsets, sizes): image b is buffer[offsets[b] : offsets[b] + sizes[b]], byte for byte what
+    write_codes writes for codes_list[b]."""
+    lib = _lib.load()
+    B = len(codes_list)
+    if B == 0 or B > MAX_BATCH:
+        raise _lib.SwcError(f"pack_batch: {B} utterances (1..{MAX_BATCH})")
+    device = codes_list[0].device
+    for c in codes_list:
+        if c.dim() != 2 or c.shape[0] != GROUPS:
+            raise _lib.SwcError(f"pack_batch: expected ({GROUPS}, T) codes, got {tuple(c.shape)}")
+        if not c.is_cuda or c.device != device:
+            raise _lib.SwcError("pack_batch: expected tensors on one HIP device")
+    n = [int(c.shape[1]) for c in codes_list]
+    if max(n) > MAX_FRAMES:
+        raise _lib.SwcError(f"pack_batch: an utterance of {max(n)} frames (at most {MAX_FRAMES})")
+    # one element size per launch: that of the utterances that hold codes (an empty one is not read, whatever its type)
+    kinds = {c.dtype for c, k in zip(codes_list, n) if k}
+    dt = torch.int64 if kinds == {torch.int64} else torch.int32
+    rows = [c if k == 0 or (c.dtype == dt and c.stride(1) == 1) else c.to(dt).contiguous() for c, k in zip(codes_list, n)]
+    es = 4 if dt == torch.int32 else 8
+    sizes = [image_bytes(k) for k in n]
+    if offsets is None:
+        offsets, pos = [], 0
+        for s in sizes:
+            offsets.append(pos)
+            pos += s
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != B:
+        raise _lib.SwcError(f"pack_batch: {len(offsets)} offsets for {B} utterances")
+    end = max(o + s for o, s in zip(offsets, sizes))
+    if out is None:
+        out = torch.empty(end, dtype=torch.uint8, device=device)
+    elif not out.is_cuda or out.device != device or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise _lib.SwcError("pack_batch: out must be a contiguous 1-D uint8 tensor on the codes' device")
+    # the kernel takes the layout from device arrays: that the images fit and do not overlap is checked here
+    spans = sorted(zip(offsets, sizes))
+    if spans[0][0] < 0 or end > out.numel() or any(a + s > b for (a, s), (b, _) in zip(spans, spans[1:])):
+        raise _lib.SwcError(f"pack_batch: the images overlap or leave the buffer of {out.numel()} bytes "
+                            f"(offsets {offsets}, sizes {sizes})")
+    meta = _meta([r.data_ptr() if k else 0 for r, k in zip(rows, n)] + [r.stride(0) if k else 0 for r, k in zip(rows, n)] + n + offsets,
+                 device)
+    with torch.cuda.device(device):
+        _lib.check(lib.swc_codes_pack_batch(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:3 * B]), _ptr(meta[3 * B:]), es,
+                                            _ptr(out), out.numel(), max(n), B, _stream()), "swc_codes_pack_batch")
+    return out, offsets, sizes
+
+
+def unpack_batch(buffer, payload_offsets, n_frames, n_codes=None, bad=None, L=None, out=None):
+    """The inverse in one launch (swc_codes_unpack_batch): payload b = the 11 n_frames[b] bytes of the device uint8 `buffer`
+    at payload_offsets[b] -> (codes (8, B, L) int32, zero from n_frames[b] to L — the batch decode_padded takes —, the list of
+    its views codes[:, b, :n_frames[b]]).  L defaults to the longest utterance (at least 1).
+    n_codes + bad: `bad` (a zeroed device int32 tensor of one element) is incremented once per unpacked value >= n_codes,
+    the codebook size of the model the codes are meant for; values pass through unchanged.
+    out: an int32 device view (8, B, L) with unit stride along L to write into (strided windows: tests)."""
+    lib = _lib.load()
+    B = len(n_frames)
+    n = [int(v) for v in n_frames]
+    offs = [int(o) for o in payload_offsets]
+    if B == 0 or B > MAX_BATCH or len(offs) != B:
+        raise _lib.SwcError(f"unpack_batch: {B} utterances (1..{MAX_BATCH}) with {len(offs)} offsets")
+    if (not buffer.is_cuda or buffer.dtype != torch.uint8 or buffer.dim() != 1 or not buffer.is_contiguous()
+            or any(k < 0 or o < 0 or o + FRAME_BYTES * k > buffer.numel() for o, k in zip(offs, n))):
+        raise _lib.SwcError("unpack_batch: expected a contiguous device uint8 buffer that holds every payload")
+    device = buffer.device
+    if out is None:
+        L = max(max(n), 1) if L is None else int(L)
+        out = torch.empty((GROUPS, B, L), dtype=torch.int32, device=device)
+    elif (out.device != device or out.dtype != torch.int32 or out.dim() != 3 or out.shape[0] != GROUPS or out.shape[1] != B
+          or (out.shape[2] > 1 and out.stride(2) != 1) or (L is not None and L != out.shape[2])):
+        raise _lib.SwcError(f"unpack_batch: out must be an int32 ({GROUPS}, {B}, L) device view with unit stride along L")
+    L = out.shape[2]
+    if max(n) > L or L > MAX_FRAMES:
+        raise _lib.SwcError(f"unpack_batch: L={L} for utterances of up to {max(n)} frames (at most {MAX_FRAMES})")
+    if (n_codes is None) != (bad is None):
+        raise _lib.SwcError("unpack_batch: n_codes and bad go together")
+    if bad is not None and (bad.device != device or bad.dtype != torch.int32 or bad.numel() != 1):
+        raise _lib.SwcError("unpack_batch: bad must be one int32 on the buffer's device")
+    ldb = out.stride(1) if B > 1 else L   # (the stride of a dimension of size 1 says nothing)
+    ldg = out.stride(0)
+    meta = _meta(offs + n, device)
+    with torch.cuda.device(device):
+        _lib.check(lib.swc_codes_unpack_batch(_ptr(buffer), buffer.numel(), _ptr(meta[:B]), _ptr(meta[B:]), _ptr(out), ldg, ldb, L,
+                                              B, 1 << BITS if n_codes is None else int(n_codes), _ptr(bad), _stream()),
+                   "swc_codes_unpack_batch")
+    return out, [out[:, b, :k] for b, k in enumerate(n)]
+
+
+_TLS = threading.local()
+
+
+def _pinned(tls, nbytes):
+    """the calling thread's pinned byte staging buffer of `tls` (grown on demand, re-used); a copy that still reads or
+    writes it (see the event the users leave) is waited for first"""
+    ev = getattr(tls, "codes_ev", None)
+    if ev is not None:
+        ev.synchronize()
+        tls.codes_ev = None
+    buf = getattr(tls, "codes_buf", None)
+    if buf is None or buf.numel() < nbytes:
+        with torch.inference_mode(False):   # (written in place by later calls, whatever mode the first caller was in)
+            buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
+        tls.codes_buf = buf
+    return buf
+
+
+def images_to_host(packed, tls=None):
+    """pack_batch's result -> the images as views of the calling thread's pinned buffer (uint8 host tensors): ONE device-to-host
+    copy, waited for.  The views are valid until this thread stages its next batch."""
+    buf, offsets, sizes = packed
+    end = max(o + s for o, s in zip(offsets, sizes))
+    host = _pinned(_TLS if tls is None else tls, end)
+    with torch.cuda.device(buf.device):
+        host[:end].copy_(buf[:end], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    return [host[o:o + s] for o, s in zip(offsets, sizes)]
+
+
+def payloads_to_device(payloads, n_frames, device, n_codes=None, bad=None, tls=None):
+    """B payloads (bytes-like, 11 n_frames[b] bytes each) -> unpack_batch's result on `device`: the payloads are laid back to
+    back into the calling thread's pinned buffer, cross as ONE host-to-device copy and are unpacked by one launch."""
+    device = torch.device(device)
+    n = [int(v) for v in n_frames]
+    offs, pos = [], 0
+    for p, k in zip(payloads, n):
+        if len(p) != FRAME_BYTES * k:
+            raise _lib.SwcError(f"payloads_to_device: a payload of {len(p)} bytes for {k} frames")
+        offs.append(pos)
+        pos += len(p)
+    tls = _TLS if tls is None else tls
+    host = _pinned(tls, pos)
+    view = host.numpy()
+    for p, o in zip(payloads, offs):
+        if len(p):
+            view[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+    with torch.cuda.device(device):
+        dev = torch.empty(max(pos, 1), dtype=torch.uint8, device=device)
+        dev[:pos].copy_(host[:pos], non_blocking=True)
+        tls.codes_ev = torch.cuda.Event()
+        tls.codes_ev.record()
+    return unpack_batch(dev, offs, n, n_codes=n_codes, bad=bad)
+
+
+def write_codes_batch(paths, codes_list):
+    """write_codes for a batch: one pack launch, one device-to-host copy into pinned memory, every file a slice of it.
+    The files are those write_codes writes."""
+    if len(paths) != len(codes_list):
+        raise ValueError(f"write_codes_batch: {len(paths)} paths for {len(codes_list)} utterances")
+    if not paths:
+        return
+    for path, image in zip(paths, images_to_host(pack_batch(codes_list))):
+        with open(path, "wb") as f:
+            f.write(image.numpy())
+
+
+def read_images(blobs, names, device="cuda", n_codes=None, tls=None):
+    """file images (bytes-like) -> (codes (8, B, L) int32 zero padded, per-utterance views, indices of the utterances that hold
+    a value >= n_codes; always [] without n_codes).  Headers are parsed and validated on the host (parse_header, ValueError
+    naming names[i]); then one copy and one launch.  With n_codes the counter is read back (synchronises) before returning."""
+    n = [parse_header(b, name) for b, name in zip(blobs, names)]
+    device = torch.device(device)
+    bad = torch.zeros(1, dtype=torch.int32, device=device) if n_codes is not None else None
+    codes, views = payloads_to_device([memoryview(b)[HEADER_BYTES:HEADER_BYTES + FRAME_BYTES * k] for b, k in zip(blobs, n)], n,
+                                      device, n_codes=n_codes, bad=bad, tls=tls)
+    wrong = []
+    if bad is not None and int(bad.item()):   # the rare path: say which utterances
+        wrong = [i for i, v in enumerate(views) if v.numel() and int(v.max()) >= n_codes]
+    return codes, views, wrong
+
+
+def read_codes_batch(paths, device="cuda", n_codes=None):
+    """read_codes for a batch -> list of device IntTensor (8, T_b), views of one zero-padded batch.  n_codes (the codebook size
+    of the model the codes are for): a file that holds a larger value raises ValueError naming it."""
+    blobs = []
+    for path in paths:
+        with open(path, "rb") as f:
+            blobs.append(f.read())
+    if not blobs:
+        return []
+    _, views, wrong = read_images(blobs, paths, device, n_codes=n_codes)
+    if wrong:
+        raise ValueError(f"{', '.join(str(paths[i]) for i in wrong)}: code values outside the codebook of {n_codes} entries "
+                         "(a corrupt file, or codes of another model)")
+    return views

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 import yaml
 
-from . import ops, packed, spec, trace
+from . import bitstream, ops, packed, spec, trace
 from ._lib import SwcError
 
 # precision presets: (encode-side GEMM operands, decode-side GEMM operands)
@@ -1411,6 +1411,34 @@ class AudioCodec(nn.Module):
             for k in range(a, b):
                 out[order[k]] = wav[k - a, : n[k] * up]
         return {"syn_wav_list": out}
+
+    @_on_model_device
+    @torch.inference_mode()
+    def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
+        """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
+        11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one
+        device-to-host copy for the batch."""
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+        if not codes:
+            return []
+        return [v.numpy().tobytes() for v in bitstream.images_to_host(bitstream.pack_batch(codes))]
+
+    @_on_model_device
+    @torch.inference_mode()
+    def decode_bytes(self, blobs, overlap_seconds=10, device=torch.device("cuda")):
+        """decode() from compressed data: blobs = SWC1 file images (bytes-like) -> {"syn_wav_list": [FloatTensor(T_i * 1280)]},
+        the waveforms decode() gives for the codes the images hold.  Headers are checked on the host (ValueError naming the
+        blob), one copy and one unpack launch bring the batch to the device, and the decoder does not run before the count
+        of values outside this model's codebook is known to be zero: SwcError names the utterances otherwise."""
+        if len(blobs) == 0:
+            return {"syn_wav_list": []}
+        dev = self._resolve_device(device)
+        n_codes = math.prod(self.fsq_levels)
+        _, views, wrong = bitstream.read_images(blobs, [f"blob {i}" for i in range(len(blobs))], dev, n_codes=n_codes)
+        if wrong:
+            raise SwcError(f"decode_bytes: utterances {wrong} hold code values >= {n_codes}, the codebook size of this model "
+                           "(corrupt data, or codes of another model)")
+        return self.decode(views, overlap_seconds=overlap_seconds, device=device)
 
     @_on_model_device
     @torch.inference_mode()

@@ -163,6 +163,20 @@ class HostStager:
                     out[i] = y[k, : n_out[k]]
         return out
 
+    def codes_to_host(self, codes_list):
+        """encode()'s codes_list -> the utterances' SWC1 file images (bitstream.py) as host uint8 views of this thread's pinned
+        byte buffer: one pack launch and one device-to-host copy per batch, where bitstream.write_codes costs a launch, a
+        synchronising copy and an allocation per utterance.  The views hold until this thread stages its next batch."""
+        from . import bitstream
+        return bitstream.images_to_host(bitstream.pack_batch(codes_list), tls=self._tls)
+
+    def codes_to_device(self, payloads, n_frames, device, n_codes=None, bad=None):
+        """the payloads of B code files (bytes-like, 11 n_frames[b] bytes each; bitstream.parse_header gives n_frames) ->
+        (codes (8, B, L) int32 zero padded, per-utterance views) on `device`: back to back in the pinned byte buffer, ONE
+        host-to-device copy, one unpack launch.  n_codes / bad: the validation counter of bitstream.unpack_batch."""
+        from . import bitstream
+        return bitstream.payloads_to_device(payloads, n_frames, device, n_codes=n_codes, bad=bad, tls=self._tls)
+
     @staticmethod
     def _by_buffer(tensors):
         """tensors grouped by the buffer they are views of: [(base or None, [indices])].  decode() returns rows of ONE padded
