@@ -180,7 +180,7 @@ int swc_pack_rows(const void* src, void* dst, const int32_t* row_start, const in
  * `w_stream` is the pair (pwconv1.weight [I][C], pwconv2.weight [C][I]) in bf16, re-ordered ONCE at load by
  * swc_convnext_pack into the order in which each wave consumes 1 KiB MFMA operand fragments
  * (swc_convnext_stream_bytes(C, I) bytes, 0 for an unsupported geometry).  bf16 operands, f32 accumulation; GELU is the
- * refit sigmoid form of the bf16 swc_gemm epilogue (|error| <= 2.7e-4).  The pack step takes the block's gamma: builds with
+ * refit sigmoid form of the bf16 swc_gemm epilogue (|error| <= 2.71e-4).  The pack step takes the block's gamma: builds with
  * -DCX_RES_ACC=1 (a measured build option, not the default) fold it into pwconv2's rows and start pwconv2's accumulators at
  * x + gamma * b2; the gamma / b2 arguments of swc_convnext_mlp / swc_convnext_block must be the ones the stream was packed with.
  */
@@ -231,7 +231,7 @@ int swc_convnext64_mlp(const void* y, const void* w_stream, const float* b1, con
  * projection (self_attn_layer_norm, modules.py:216), so neither LayerNorm of the layer is a launch of its own and the
  * [M][F] hidden activations never exist in memory (two swc_gemm calls write and re-read them: 98 MB per layer at
  * 32 x 10 s).  bf16 operands, f32 accumulation; GELU is the refit sigmoid form of the bf16 swc_gemm epilogue
- * (|error| <= 2.7e-4).  Built for D = 768, F % 256 == 0 (the shipped 768 / 3072); other geometries return SWC_E_ARG and the
+ * (|error| <= 2.71e-4).  Built for D = 768, F % 256 == 0 (the shipped 768 / 3072); other geometries return SWC_E_ARG and the
  * caller runs swc_layernorm + two swc_gemm calls instead.  `w_stream` is the pair (fc1.weight [F][D], fc2.weight [D][F]) in
  * bf16, re-ordered ONCE at load by swc_mlp_pack into the order in which each wave consumes 1 KiB MFMA operand fragments
  * (swc_mlp_stream_bytes(D, F) bytes, 0 for an unsupported geometry).  Padded rows are computed like any other row, as in

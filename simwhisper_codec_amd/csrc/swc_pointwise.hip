@@ -297,7 +297,12 @@ void dwconv7_ln_kernel(const float* __restrict__ x, OutT* __restrict__ y,
             for (int u = 0; u < DW_FG; ++u) sum[u] = wave_sum_dpp(sum[u]);
 #pragma unroll
             for (int u = 0; u < DW_FG; ++u) {
-                const float mean = sum[u] * inv_c;
+                // a true division (as swc_layernorm, swc_mlp_block and swc_proj_ln do): 1 / C is inexact when C is no power of two
+                // (768), and the product then puts a systematic rounding of its own on every mean.  On a constant row x = c that
+                // alone made c - mean non-zero, and (c - mean) rstd reaches +-1 once |c| 2^-24 exceeds sqrt(eps).  The division
+                // removes that error; what stays is the rounding of the sum itself (rnd(12 c) / 12 need not round back to c for
+                // every c).  Same bits as the product for C = 2^n (the path's 512 and 64).
+                const float mean = sum[u] / (float)C;
                 sq[u] = 0.f;
 #pragma unroll
                 for (int k = 0; k < NK; ++k) {
