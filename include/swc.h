@@ -124,6 +124,26 @@ typedef struct swc_gemm_args {
     float out_scale; /* F16S / FP8 outputs only: 2^s applied before the split / conversion; 0 means 1 */
 } swc_gemm_args;
 int swc_gemm(const swc_gemm_args* args, void* stream);
+/*
+ * What swc_gemm would launch for `args`, without launching anything (host arithmetic only: no device is needed, no pointer
+ * is dereferenced; `plan` is a HOST struct).  swc_gemm launches exactly what this reports — both read the same chooser — so a
+ * caller, a benchmark or a test can name the kernel and the work walk of a call: once n_tiles_m * n_tiles_n exceeds `slots`
+ * the grid is capped at `slots` resident workgroups and every workgroup walks several tiles (the tile sequence is cut into 8
+ * contiguous per-XCD chunks, walked in bands of `band` row panels).  Same argument checks and error codes as swc_gemm; on an
+ * error, and for M == 0 (nothing is launched), every field is 0.  No reference counterpart (ATen picks its own kernels).
+ */
+typedef struct swc_gemm_plan_out {
+    int32_t a_dtype;              /* operand mode: SWC_F32 | SWC_BF16 | SWC_F16S | SWC_FP8 */
+    int32_t tile_m, tile_n;       /* output rows / columns per tile: 256 | 192 | 128 x 256 (8 waves), 128 | 64 x 128 (4 waves) */
+    int32_t waves;                /* waves per workgroup: 8 or 4 */
+    int32_t plain;                /* 1: plain GEMM staging; 0: implicit-conv staging (taps, stride, pad, K tail, wide row pitch) */
+    int32_t act_body;             /* epilogue body compiled in: 0 no activation, 1 GELU, 2 chosen at run time by args->act */
+    int32_t k_slice, k_slices;    /* logical elements of K per LDS slice; slices per tap = ceil(K / k_slice) */
+    int32_t n_tiles_m, n_tiles_n; /* tiles along M and N */
+    int32_t band;                 /* row panels per band of the tile order: 1 (row-major) or 4 */
+    int32_t grid, slots;          /* workgroups launched; resident workgroups of the geometry (256 or 512) */
+} swc_gemm_plan_out;
+int swc_gemm_plan(const swc_gemm_args* args, swc_gemm_plan_out* plan);
 
 /*
  * Varlen multi-head self-attention, head_dim 64, non-causal, keys >= len masked.
@@ -301,6 +321,24 @@ int swc_proj_ln(const void* a_f16s, int64_t lda, const void* w_stream, const flo
 int swc_dwconv7_ln(const float* x, void* y, const float* w, const float* bias, const float* ln_w,
                    const float* ln_b, int32_t B, int32_t T, int32_t C, float eps, int32_t y_dtype,
                    void* stream);
+/*
+ * What swc_dwconv7_ln would launch for (B, T, C, y_dtype), without launching anything (host arithmetic only; `plan` is a HOST
+ * struct).  swc_dwconv7_ln launches exactly what this reports.  An utterance is cut into nst = ceil(T / S) strips of S frames;
+ * once B * nst exceeds `slots` every workgroup walks `per` >= 2 consecutive strips (re-using the halo rows it just loaded,
+ * possibly from the last strip of one utterance into the first of the next; the last workgroup's walk may be shorter).  Same
+ * checks of C and y_dtype as swc_dwconv7_ln; on an error every field is 0, for B * T <= 0 (nothing is launched) the walk
+ * fields are.
+ */
+typedef struct swc_dwconv7_ln_plan_out {
+    int32_t S;            /* frames per strip: 32 (C <= 256) or 16 */
+    int32_t NK;           /* float4 per lane of a row: 1 (C <= 256), 2 (C <= 512), 4 */
+    int32_t FULL;         /* 1: C == 256 * NK, the kernel without per-lane column predicates */
+    int32_t nst, nstrips; /* strips per utterance, strips of the call (B * nst) */
+    int32_t slots;        /* resident workgroups: 512, or 256 where one workgroup's LDS fills a CU */
+    int32_t per;          /* consecutive strips per workgroup */
+    int32_t grid;         /* workgroups launched (a multiple of 8) */
+} swc_dwconv7_ln_plan_out;
+int swc_dwconv7_ln_plan(int32_t B, int32_t T, int32_t C, int32_t y_dtype, swc_dwconv7_ln_plan_out* plan);
 
 /*
  * Anti-aliased SnakeBeta (Activation1d): replicate-pad, 2x kaiser-sinc upsample,

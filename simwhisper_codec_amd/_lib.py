@@ -37,16 +37,29 @@ class GemmArgs(C.Structure):
     ]
 
 
+class GemmPlan(C.Structure):
+    """swc_gemm_plan_out of include/swc.h"""
+    _fields_ = [(n, C.c_int32) for n in ("a_dtype", "tile_m", "tile_n", "waves", "plain", "act_body", "k_slice", "k_slices",
+                                         "n_tiles_m", "n_tiles_n", "band", "grid", "slots")]
+
+
+class Dwconv7LnPlan(C.Structure):
+    """swc_dwconv7_ln_plan_out of include/swc.h"""
+    _fields_ = [(n, C.c_int32) for n in ("S", "NK", "FULL", "nst", "nstrips", "slots", "per", "grid")]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes (all return int); mirrors include/swc.h one to one
 SIGNATURES = {
     "swc_gemm": [C.POINTER(GemmArgs), _P],
+    "swc_gemm_plan": [C.POINTER(GemmArgs), C.POINTER(GemmPlan)],
     "swc_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
     "swc_attention_ex": [_P, _P, _P, _I, _I, _I, _I, _P],
     "swc_attention16": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "swc_layernorm": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P],
     "swc_dwconv7_ln": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P],
+    "swc_dwconv7_ln_plan": [_I, _I, _I, _I, C.POINTER(Dwconv7LnPlan)],
     "swc_snake_aa": [_P, _P, _P, _P, C.POINTER(_F), _I, _I, _I, _I, _P],
     "swc_fsq_encode": [_P, _L, _P, _P, _P, C.POINTER(_F), _I, _I, _I, _I, _P],
     "swc_fsq_decode": [_P, _P, _L, _P, _I, _I, _I, _P],

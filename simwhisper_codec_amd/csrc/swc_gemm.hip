@@ -19,6 +19,7 @@
 // The product is computed TRANSPOSED (weight fragment = MFMA row operand) with the weight rows of a
 // fragment taken as {16a + 4j + b}: lane (fr, fh) then owns, for activation row 16i + fr, the 16
 // CONTIGUOUS output columns 16fh + 4j + e — 64-byte vector stores, full lines per row across fh.
+#include <string.h>
 #include "swc_mfma.h"
 
 // Geometry overrides for A/B measurements exist only in tuning builds (-DSWC_TUNING, tools/build_variant.sh): the
@@ -760,62 +761,60 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, 2) void gemm_kernel(GemmP p)
     }
 }
 
+// Everything the host decides about one call: the kernel instance (operand mode, tile, staging, epilogue body) and its
+// work walk (tile counts, band, grid).  gemm_plan() is the only place that decides; swc_gemm launches what it says and
+// swc_gemm_plan reports it.
+struct GemmPlan {
+    int mode;          // SWC_F32 | SWC_BF16 | SWC_F16S | SWC_FP8: the operands' format
+    int mt, wm, wn;    // tile = (wm * mt * 16) rows x (wn * 64) columns on wm * wn waves
+    int plain;         // 1: plain GEMM staging, 0: implicit-conv staging (taps, strides, K tails, wide row pitches)
+    int act_body;      // epilogue body compiled in: 0 no activation, 1 GELU, 2 chosen at run time by `act`
+    int bk;            // logical elements of K per slice
+    int kc_per_tap;    // ceil(K / bk)
+    int n_tiles_m, n_tiles_n;
+    int band;          // tile-order band height (row panels), see the kernel
+    long slots, grid;  // resident workgroups of the geometry; launched workgroups (grid < tiles: every workgroup walks)
+    int nt_mode;       // GemmP::nt_mode
+    int stagger;       // GemmP::stagger
+};
+
 template <int MODE, typename OutT, int MT, int WM, int WN, bool PLAIN, int RB = 128, int ACT = 2>
-int launch_k(GemmP p, hipStream_t s) {
+int launch_k(GemmP p, const GemmPlan& g, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * 64;
     constexpr int LDS = 2 * (BM + BN) * RB;
-    {
-        constexpr int BK = RB / (MODE == SWC_BF16 ? 2 : (MODE == SWC_FP8 ? 1 : 4));
-        p.kc_per_tap = (p.K + BK - 1) / BK;
-    }
-    p.n_tiles_n = (p.N + BN - 1) / BN;
-    p.n_tiles_m = (p.M + BM - 1) / BM;
-    {
-        const int forced = tuning_env("SWC_GEMM_BAND");
-        p.band = forced > 0 ? forced : (p.n_tiles_n >= 12 ? 4 : 1);
-    }
-    const long nwg = (long)p.n_tiles_n * p.n_tiles_m;
-    if (nwg >= (1L << 30)) {
-        swc_set_error("swc_gemm: grid too large");
+    constexpr int BK = RB / (MODE == SWC_BF16 ? 2 : (MODE == SWC_FP8 ? 1 : 4));
+    if (g.mode != MODE || g.mt != MT || g.wm != WM || g.wn != WN || g.plain != (PLAIN ? 1 : 0) || g.act_body != ACT || g.bk != BK) {
+        swc_set_error("swc_gemm: the launched kernel is not the planned one");
         return SWC_E_ARG;
     }
+    p.kc_per_tap = g.kc_per_tap;
+    p.n_tiles_n = g.n_tiles_n;
+    p.n_tiles_m = g.n_tiles_m;
+    p.band = g.band;
+    p.nt_mode = g.nt_mode;
+    p.stagger = g.stagger;
     auto kern = gemm_kernel<MODE, OutT, MT, WM, WN, PLAIN, RB, ACT>;
     if (LDS > 64 * 1024) SWC_ENABLE_LDS(kern, LDS, "swc_gemm");
-    // persistent grid: one workgroup per CU for the 8-wave geometries, two for the 4-wave one (256 CUs)
-    const int persist = tuning_env("SWC_GEMM_NOPERSIST") ? 0 : 1;
-    const long slots = 256L * (WM * WN == 4 ? 2 : 1);
-    const long grid = (persist && nwg > slots) ? slots : nwg;
-    // Non-temporal epilogue stores (profiles/r03_gemm_store_policy.txt): alone on the chip the split-f16 fc2 gains 12 % from
-    // them (one tile per workgroup, whole 256-byte row pieces behind a long K loop), every other shape loses 0 - 40 %; inside
-    // the pipeline the same fc2 / out-proj launches run 1 % SLOWER with them (129 -> 130 us, same-box rocprof A/B): off.
-    // The mode stays selectable in tuning builds.
-    p.nt_mode = tuning_env("SWC_GEMM_NT", 0);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WM * WN * 64), LDS, s, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)g.grid), dim3(WM * WN * 64), LDS, s, p);
     return SWC_OK;
 }
 
 template <int MODE, typename OutT, int MT, int WM, int WN, int RB = 128>
-int launch(GemmP p, hipStream_t s) {
-    constexpr int BK = RB / (MODE == SWC_BF16 ? 2 : (MODE == SWC_FP8 ? 1 : 4));
-    const long es = MODE == SWC_BF16 ? 2 : (MODE == SWC_FP8 ? 1 : 4);
-    const bool plain = (p.taps == 1) && (p.K % BK == 0) && (p.stride == 1) && (p.pad == 0) && (p.t_in == p.t_out) &&
-                       p.lda * es < (1L << 24) && p.ldw * es < (1L << 24);  // 24-bit row pitch: offsets by v_mul_u32_u24
+int launch(GemmP p, const GemmPlan& g, hipStream_t s) {
     // plain GEMMs with 16- / 8-bit outputs (qkv, fc1 + GELU, pwconv1 + GELU): the activation is compiled in, one epilogue
     // body per kernel
     if constexpr (sizeof(OutT) < 4 && MODE != SWC_F32) {
-        if (plain) return p.act == SWC_ACT_GELU ? launch_k<MODE, OutT, MT, WM, WN, true, RB, 1>(p, s) : launch_k<MODE, OutT, MT, WM, WN, true, RB, 0>(p, s);
-        return launch_k<MODE, OutT, MT, WM, WN, false, RB, 2>(p, s);
+        if (g.plain) return g.act_body == 1 ? launch_k<MODE, OutT, MT, WM, WN, true, RB, 1>(p, g, s) : launch_k<MODE, OutT, MT, WM, WN, true, RB, 0>(p, g, s);
+        return launch_k<MODE, OutT, MT, WM, WN, false, RB, 2>(p, g, s);
     } else {
-        return plain ? launch_k<MODE, OutT, MT, WM, WN, true, RB>(p, s) : launch_k<MODE, OutT, MT, WM, WN, false, RB>(p, s);
+        return g.plain ? launch_k<MODE, OutT, MT, WM, WN, true, RB>(p, g, s) : launch_k<MODE, OutT, MT, WM, WN, false, RB>(p, g, s);
     }
 }
 
-}  // namespace
-
 // SWC_GEMM_TILE=128|256 overrides the geometry choice (tuning builds only).
-static int tile_override() { return tuning_env("SWC_GEMM_TILE"); }
+int tile_override() { return tuning_env("SWC_GEMM_TILE"); }
 
-extern "C" int swc_gemm(const swc_gemm_args* a, void* stream) {
+int gemm_check_args(const swc_gemm_args* a) {
     SWC_CHECK_ARG(a != nullptr, "swc_gemm: null args");
     SWC_CHECK_ARG(a->A && a->W && a->C, "swc_gemm: null operand");
     SWC_CHECK_ARG(a->M >= 0 && a->N > 0 && a->K > 0, "swc_gemm: bad M/N/K %d %d %d", a->M, a->N, a->K);
@@ -844,47 +843,28 @@ extern "C" int swc_gemm(const swc_gemm_args* a, void* stream) {
     SWC_CHECK_ARG(a->ldw >= (int64_t)a->taps * a->K, "swc_gemm: ldw < taps*K");
     SWC_CHECK_ARG(a->lda >= a->K && a->ldc >= a->N, "swc_gemm: lda < K or ldc < N");
     SWC_CHECK_ARG(!a->residual || a->ldr >= a->N, "swc_gemm: ldr < N");
-    if (a->M == 0) return SWC_OK;
+    return SWC_OK;
+}
 
-    GemmP p;
-    p.A = (const char*)a->A;
-    p.W = (const char*)a->W;
-    p.C = a->C;
-    p.bias = a->bias;
-    p.gamma = a->gamma;
-    p.residual = a->residual;
-    p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldr = a->ldr;
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.taps = a->taps; p.dil = a->dil; p.stride = a->stride; p.pad = a->pad;
-    p.t_in = a->t_in; p.t_out = a->t_out;
-    p.act = a->act;
-    p.alpha = a->alpha == 0.0f ? 1.0f : a->alpha;
-    p.out_scale = a->out_scale == 0.0f ? 1.0f : a->out_scale;
-    const int bk = bf ? 64 : (f8 ? 128 : 32);
-    p.kc_per_tap = (a->K + bk - 1) / bk;
-    p.n_tiles_n = p.n_tiles_m = 0;
-    p.nt_mode = -1;  // chosen per geometry in launch_k (tuning builds: SWC_GEMM_NT forces 0 / 1 / 2)
-    p.stagger = tuning_env("SWC_GEMM_STAGGER", 0);
-    p.sat = swc_sat_counter();
-    hipStream_t s = (hipStream_t)stream;
+// The chooser.  `a` has passed gemm_check_args and M > 0.
+int gemm_plan(const swc_gemm_args* a, GemmPlan* g) {
+    const bool bf = a->a_dtype == SWC_BF16;
+    const bool fs = a->a_dtype == SWC_F16S;
+    const bool f8 = a->a_dtype == SWC_FP8;
+    g->mode = a->a_dtype;
     // geometry: the 256x256 / 8-wave tile pays off when its grid still fills the 256 CUs
     const long big_tiles = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
-    bool big = (bf || f8) && a->N >= 256 && big_tiles >= 96;
+    const bool fills = a->N >= 256 && big_tiles >= 96;
+    bool big = (bf || f8 || fs) && fills;
     if (tile_override() == 128) big = false;
-    if (tile_override() == 256) big = bf || f8;
-    int rc;
-    const int cd = a->c_dtype;
-#define SWC_LAUNCH(MODE, MT, WM, WN)                                                        \
-    (cd == SWC_BF16 ? launch<MODE, bf16_t, MT, WM, WN>(p, s)                                 \
-                    : (cd == SWC_F16S ? launch<MODE, f16s_t, MT, WM, WN>(p, s) : launch<MODE, float, MT, WM, WN>(p, s)))
-    // 16-bit outputs come in the operands' own format only (checked above): no split-f16 -> bf16 or bf16 -> split-f16 kernels
-#define SWC_LAUNCH_B(MT, WM, WN) (cd == SWC_BF16 ? launch<SWC_BF16, bf16_t, MT, WM, WN>(p, s) : launch<SWC_BF16, float, MT, WM, WN>(p, s))
-#define SWC_LAUNCH_S(MT, WM, WN) (cd == SWC_F16S ? launch<SWC_F16S, f16s_t, MT, WM, WN>(p, s) : launch<SWC_F16S, float, MT, WM, WN>(p, s))
+    if (tile_override() == 256) big = bf || f8 || fs;
     // 8-wave geometries differ only in the rows per tile (256 / 192 / 128 x 256 columns): pick the one whose grid
     // quantises best over the 256 CUs.  cost ~ rounds x (rows + fixed per-tile overhead); e.g. M = 16000, N = 768:
     // 189 tiles of 256 rows leave a quarter of the chip idle, 252 tiles of 192 rows fill it in one round.
     int mt = 8;
-    if (((bf || f8) && big) || (fs && a->N >= 256 && big_tiles >= 96)) {
+    // (`fills` matters in tuning builds only: split-f16 forced onto the 8-wave tile by SWC_GEMM_TILE=256 without a filling
+    // grid keeps 256 rows)
+    if (big && (!fs || fills)) {
         const int forced = tuning_env("SWC_GEMM_MT");
         const long ntn = (a->N + 255) / 256;
         double best = 1e30;
@@ -900,28 +880,123 @@ extern "C" int swc_gemm(const swc_gemm_args* a, void* stream) {
     const int small_env = tuning_env("SWC_GEMM_SMALL", 1);
     const long tiles128 = (long)((a->M + 127) / 128) * ((a->N + 127) / 128);
     const bool half_rows = small_env && tiles128 < 384 && a->M >= 512;
-    if (f8) {
+    if (big) {
+        g->mt = mt; g->wm = 2; g->wn = 4;
+    } else {
+        g->mt = ((bf || fs) && half_rows) ? 2 : 4; g->wm = 2; g->wn = 2;
+    }
+    const int BM = g->wm * g->mt * 16, BN = g->wn * 64;
+    const long es = bf ? 2 : (f8 ? 1 : 4);
+    g->bk = (int)(128 / es);
+    g->plain = ((a->taps == 1) && (a->K % g->bk == 0) && (a->stride == 1) && (a->pad == 0) && (a->t_in == a->t_out) &&
+                a->lda * es < (1L << 24) && a->ldw * es < (1L << 24))  // 24-bit row pitch: offsets by v_mul_u32_u24
+                   ? 1 : 0;
+    // plain GEMMs with 16- / 8-bit outputs: the activation is compiled in (launch)
+    g->act_body = (a->c_dtype != SWC_F32 && a->a_dtype != SWC_F32 && g->plain) ? (a->act == SWC_ACT_GELU ? 1 : 0) : 2;
+    g->kc_per_tap = (a->K + g->bk - 1) / g->bk;
+    g->n_tiles_n = (a->N + BN - 1) / BN;
+    g->n_tiles_m = (a->M + BM - 1) / BM;
+    {
+        const int forced = tuning_env("SWC_GEMM_BAND");
+        g->band = forced > 0 ? forced : (g->n_tiles_n >= 12 ? 4 : 1);
+    }
+    const long nwg = (long)g->n_tiles_n * g->n_tiles_m;
+    if (nwg >= (1L << 30)) {
+        swc_set_error("swc_gemm: grid too large");
+        return SWC_E_ARG;
+    }
+    // persistent grid: one workgroup per CU for the 8-wave geometries, two for the 4-wave one (256 CUs)
+    const int persist = tuning_env("SWC_GEMM_NOPERSIST") ? 0 : 1;
+    g->slots = 256L * (g->wm * g->wn == 4 ? 2 : 1);
+    g->grid = (persist && nwg > g->slots) ? g->slots : nwg;
+    // Non-temporal epilogue stores (profiles/r03_gemm_store_policy.txt): alone on the chip the split-f16 fc2 gains 12 % from
+    // them (one tile per workgroup, whole 256-byte row pieces behind a long K loop), every other shape loses 0 - 40 %; inside
+    // the pipeline the same fc2 / out-proj launches run 1 % SLOWER with them (129 -> 130 us, same-box rocprof A/B): off.
+    // The mode stays selectable in tuning builds.
+    g->nt_mode = tuning_env("SWC_GEMM_NT", 0);
+    g->stagger = tuning_env("SWC_GEMM_STAGGER", 0);
+    return SWC_OK;
+}
+
+}  // namespace
+
+extern "C" int swc_gemm_plan(const swc_gemm_args* a, swc_gemm_plan_out* out) {
+    SWC_CHECK_ARG(out != nullptr, "swc_gemm_plan: null plan");
+    memset(out, 0, sizeof(*out));
+    int rc = gemm_check_args(a);
+    if (rc != SWC_OK) return rc;
+    if (a->M == 0) return SWC_OK;  // swc_gemm launches nothing: grid 0
+    GemmPlan g;
+    rc = gemm_plan(a, &g);
+    if (rc != SWC_OK) return rc;
+    out->a_dtype = g.mode;
+    out->tile_m = g.wm * g.mt * 16;
+    out->tile_n = g.wn * 64;
+    out->waves = g.wm * g.wn;
+    out->plain = g.plain;
+    out->act_body = g.act_body;
+    out->k_slice = g.bk;
+    out->k_slices = g.kc_per_tap;
+    out->n_tiles_m = g.n_tiles_m;
+    out->n_tiles_n = g.n_tiles_n;
+    out->band = g.band;
+    out->grid = (int32_t)g.grid;
+    out->slots = (int32_t)g.slots;
+    return SWC_OK;
+}
+
+extern "C" int swc_gemm(const swc_gemm_args* a, void* stream) {
+    int rc = gemm_check_args(a);
+    if (rc != SWC_OK) return rc;
+    if (a->M == 0) return SWC_OK;
+    GemmPlan g;
+    rc = gemm_plan(a, &g);
+    if (rc != SWC_OK) return rc;
+
+    GemmP p;
+    p.A = (const char*)a->A;
+    p.W = (const char*)a->W;
+    p.C = a->C;
+    p.bias = a->bias;
+    p.gamma = a->gamma;
+    p.residual = a->residual;
+    p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldr = a->ldr;
+    p.M = a->M; p.N = a->N; p.K = a->K;
+    p.taps = a->taps; p.dil = a->dil; p.stride = a->stride; p.pad = a->pad;
+    p.t_in = a->t_in; p.t_out = a->t_out;
+    p.act = a->act;
+    p.alpha = a->alpha == 0.0f ? 1.0f : a->alpha;
+    p.out_scale = a->out_scale == 0.0f ? 1.0f : a->out_scale;
+    p.sat = swc_sat_counter();
+    hipStream_t s = (hipStream_t)stream;
+    const int cd = a->c_dtype;
+    const int mt = g.mt;
+    const bool big = g.wm * g.wn == 8;
+#define SWC_LAUNCH(MODE, MT, WM, WN)                                                        \
+    (cd == SWC_BF16 ? launch<MODE, bf16_t, MT, WM, WN>(p, g, s)                              \
+                    : (cd == SWC_F16S ? launch<MODE, f16s_t, MT, WM, WN>(p, g, s) : launch<MODE, float, MT, WM, WN>(p, g, s)))
+    // 16-bit outputs come in the operands' own format only (checked above): no split-f16 -> bf16 or bf16 -> split-f16 kernels
+#define SWC_LAUNCH_B(MT, WM, WN) (cd == SWC_BF16 ? launch<SWC_BF16, bf16_t, MT, WM, WN>(p, g, s) : launch<SWC_BF16, float, MT, WM, WN>(p, g, s))
+#define SWC_LAUNCH_S(MT, WM, WN) (cd == SWC_F16S ? launch<SWC_F16S, f16s_t, MT, WM, WN>(p, g, s) : launch<SWC_F16S, float, MT, WM, WN>(p, g, s))
+    if (g.mode == SWC_FP8) {
 #define SWC_LAUNCH8(MT, WM, WN)                                                   \
-    (cd == SWC_BF16 ? launch<SWC_FP8, bf16_t, MT, WM, WN>(p, s)                     \
-                    : (cd == SWC_FP8 ? launch<SWC_FP8, fp8_t, MT, WM, WN>(p, s) : launch<SWC_FP8, float, MT, WM, WN>(p, s)))
+    (cd == SWC_BF16 ? launch<SWC_FP8, bf16_t, MT, WM, WN>(p, g, s)                  \
+                    : (cd == SWC_FP8 ? launch<SWC_FP8, fp8_t, MT, WM, WN>(p, g, s) : launch<SWC_FP8, float, MT, WM, WN>(p, g, s)))
         if (big)
             rc = mt == 8 ? SWC_LAUNCH8(8, 2, 4) : (mt == 6 ? SWC_LAUNCH8(6, 2, 4) : SWC_LAUNCH8(4, 2, 4));
         else
             rc = SWC_LAUNCH8(4, 2, 2);
 #undef SWC_LAUNCH8
-    } else if (bf) {
+    } else if (g.mode == SWC_BF16) {
         if (big)
             rc = mt == 8 ? SWC_LAUNCH_B(8, 2, 4) : (mt == 6 ? SWC_LAUNCH_B(6, 2, 4) : SWC_LAUNCH_B(4, 2, 4));
         else
-            rc = half_rows ? SWC_LAUNCH_B(2, 2, 2) : SWC_LAUNCH_B(4, 2, 2);
-    } else if (fs) {
-        bool bigs = a->N >= 256 && big_tiles >= 96;
-        if (tile_override() == 128) bigs = false;
-        if (tile_override() == 256) bigs = true;
-        if (bigs)
+            rc = mt == 2 ? SWC_LAUNCH_B(2, 2, 2) : SWC_LAUNCH_B(4, 2, 2);
+    } else if (g.mode == SWC_F16S) {
+        if (big)
             rc = mt == 8 ? SWC_LAUNCH_S(8, 2, 4) : (mt == 6 ? SWC_LAUNCH_S(6, 2, 4) : SWC_LAUNCH_S(4, 2, 4));
         else
-            rc = half_rows ? SWC_LAUNCH_S(2, 2, 2) : SWC_LAUNCH_S(4, 2, 2);
+            rc = mt == 2 ? SWC_LAUNCH_S(2, 2, 2) : SWC_LAUNCH_S(4, 2, 2);
     } else {
         rc = SWC_LAUNCH(SWC_F32, 4, 2, 2);
     }

@@ -2,6 +2,7 @@
 // SnakeBeta, FSQ encode/decode, the log-mel pieces around the DFT/mel GEMMs, the
 // ConvTranspose1d col2im tail and the ISTFT spectrum + overlap-add.  All operate on
 // frame-major [B][T][C] activations so that a wave reads whole rows (C contiguous).
+#include <string.h>
 #include "swc_common.h"
 
 namespace {
@@ -862,21 +863,67 @@ extern "C" int swc_layernorm(const float* x, void* y, const float* w, const floa
     return SWC_OK;
 }
 
+// Everything the host decides about one swc_dwconv7_ln call: the kernel instance (NK float4 per lane, strips of S frames,
+// FULL rows) and its work walk.  dw_plan() is the only place that decides; swc_dwconv7_ln launches what it says and
+// swc_dwconv7_ln_plan reports it.
+struct DwPlan {
+    int S, NK, full;
+    int lds;           // bytes of LDS per workgroup
+    int nst, nstrips;  // strips per utterance, strips of the call
+    int slots;         // resident workgroups
+    int per;           // consecutive strips per workgroup
+    int grid;
+};
+
+static int dw_plan(int B, int T, int C, int y_dtype, DwPlan* g) {
+    SWC_CHECK_ARG(C > 0 && C % 4 == 0 && C <= 256 * DW_MAXV, "swc_dwconv7_ln: C=%d unsupported", C);
+    SWC_CHECK_ARG(y_dtype == SWC_F32 || y_dtype == SWC_BF16, "swc_dwconv7_ln: bad dtype");
+    // strips of 16 frames: (16+6) rows of LDS per workgroup, two workgroups per CU (register-limited)
+    if (C <= 256) { g->NK = 1; g->S = 32; }
+    else if (C <= 512) { g->NK = 2; g->S = 16; }
+    else { g->NK = 4; g->S = 16; }
+    g->full = C == 256 * g->NK ? 1 : 0;
+    g->lds = (g->S + 6) * C * 4;
+    g->nst = g->nstrips = g->per = g->grid = 0;
+    // resident workgroups: LDS-limited per CU, 256 CUs; each walks nstrips / grid strips
+    const int fit = 160 * 1024 / g->lds;
+    g->slots = 256 * (fit > 2 ? 2 : fit);  // <= 2 waves per SIMD by registers
+    if ((long)B * T <= 0) return SWC_OK;    // nothing to launch: grid 0
+    g->nst = (T + g->S - 1) / g->S;
+    g->nstrips = g->nst * B;
+    g->per = (g->nstrips + g->slots - 1) / g->slots;                  // consecutive strips per workgroup
+    g->grid = ((g->nstrips + g->per - 1) / g->per + 7) & ~7;          // multiple of 8: one contiguous strip range per XCD
+    return SWC_OK;
+}
+
 template <typename OutT, int NK, int S, bool FULL>
 static int launch_dwconv7_ln(const float* x, void* y, const float* w, const float* bias, const float* ln_w,
-                             const float* ln_b, int B, int T, int C, float eps, hipStream_t s) {
-    const int lds = (S + 6) * C * 4;
+                             const float* ln_b, int T, int C, float eps, const DwPlan& g, hipStream_t s) {
+    if (g.NK != NK || g.S != S || g.full != (FULL ? 1 : 0)) {
+        swc_set_error("swc_dwconv7_ln: the launched kernel is not the planned one");
+        return SWC_E_ARG;
+    }
     auto kern = dwconv7_ln_kernel<OutT, NK, S, FULL>;
-    if (lds > 48 * 1024) SWC_ENABLE_LDS(kern, 160 * 1024, "swc_dwconv7_ln");
-    const int nst = (T + S - 1) / S, nstrips = nst * B;
-    // resident workgroups: LDS-limited per CU, 256 CUs; each walks nstrips / grid strips
-    const int wgs = 0;
-    const int fit = 160 * 1024 / lds;
-    const int slots = 256 * (wgs > 0 ? wgs : (fit > 2 ? 2 : fit));  // <= 2 waves per SIMD by registers
-    const int per = (nstrips + slots - 1) / slots;           // consecutive strips per workgroup
-    const int grid = ((nstrips + per - 1) / per + 7) & ~7;   // multiple of 8: one contiguous strip range per XCD
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, x, (OutT*)y, w, bias, ln_w, ln_b, T, C, nst, nstrips,
-                       per, eps);
+    if (g.lds > 48 * 1024) SWC_ENABLE_LDS(kern, 160 * 1024, "swc_dwconv7_ln");
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), g.lds, s, x, (OutT*)y, w, bias, ln_w, ln_b, T, C, g.nst, g.nstrips,
+                       g.per, eps);
+    return SWC_OK;
+}
+
+extern "C" int swc_dwconv7_ln_plan(int32_t B, int32_t T, int32_t C, int32_t y_dtype, swc_dwconv7_ln_plan_out* out) {
+    SWC_CHECK_ARG(out != nullptr, "swc_dwconv7_ln_plan: null plan");
+    memset(out, 0, sizeof(*out));
+    DwPlan g;
+    const int rc = dw_plan(B, T, C, y_dtype, &g);
+    if (rc != SWC_OK) return rc;
+    out->S = g.S;
+    out->NK = g.NK;
+    out->FULL = g.full;
+    out->nst = g.nst;
+    out->nstrips = g.nstrips;
+    out->slots = g.slots;
+    out->per = g.per;
+    out->grid = g.grid;
     return SWC_OK;
 }
 
@@ -884,25 +931,24 @@ extern "C" int swc_dwconv7_ln(const float* x, void* y, const float* w, const flo
                               const float* ln_b, int32_t B, int32_t T, int32_t C, float eps, int32_t y_dtype,
                               void* stream) {
     SWC_CHECK_ARG(x && y && w && bias && ln_w && ln_b, "swc_dwconv7_ln: null pointer");
-    SWC_CHECK_ARG(C > 0 && C % 4 == 0 && C <= 256 * DW_MAXV, "swc_dwconv7_ln: C=%d unsupported", C);
-    SWC_CHECK_ARG(y_dtype == SWC_F32 || y_dtype == SWC_BF16, "swc_dwconv7_ln: bad dtype");
-    if ((long)B * T <= 0) return SWC_OK;
+    DwPlan g;
+    int rc = dw_plan(B, T, C, y_dtype, &g);
+    if (rc != SWC_OK) return rc;
+    if (g.grid == 0) return SWC_OK;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
 #define DW_GO(NK_, S_)                                                                                            \
     do {                                                                                                          \
-        if (C == 256 * NK_)                                                                                       \
+        if (g.full)                                                                                               \
             rc = y_dtype == SWC_BF16                                                                              \
-                     ? launch_dwconv7_ln<bf16_t, NK_, S_, true>(x, y, w, bias, ln_w, ln_b, B, T, C, eps, s)       \
-                     : launch_dwconv7_ln<float, NK_, S_, true>(x, y, w, bias, ln_w, ln_b, B, T, C, eps, s);       \
+                     ? launch_dwconv7_ln<bf16_t, NK_, S_, true>(x, y, w, bias, ln_w, ln_b, T, C, eps, g, s)       \
+                     : launch_dwconv7_ln<float, NK_, S_, true>(x, y, w, bias, ln_w, ln_b, T, C, eps, g, s);       \
         else                                                                                                      \
             rc = y_dtype == SWC_BF16                                                                              \
-                     ? launch_dwconv7_ln<bf16_t, NK_, S_, false>(x, y, w, bias, ln_w, ln_b, B, T, C, eps, s)      \
-                     : launch_dwconv7_ln<float, NK_, S_, false>(x, y, w, bias, ln_w, ln_b, B, T, C, eps, s);      \
+                     ? launch_dwconv7_ln<bf16_t, NK_, S_, false>(x, y, w, bias, ln_w, ln_b, T, C, eps, g, s)      \
+                     : launch_dwconv7_ln<float, NK_, S_, false>(x, y, w, bias, ln_w, ln_b, T, C, eps, g, s);      \
     } while (0)
-    // strips of 16 frames: (16+6) rows of LDS per workgroup, two workgroups per CU (register-limited)
-    if (C <= 256) { DW_GO(1, 32); }
-    else if (C <= 512) { DW_GO(2, 16); }
+    if (g.NK == 1) { DW_GO(1, 32); }
+    else if (g.NK == 2) { DW_GO(2, 16); }
     else { DW_GO(4, 16); }
 #undef DW_GO
     if (rc != SWC_OK) return rc;

@@ -47,12 +47,10 @@ def _chk(t, name, dtype=None):
     return t
 
 
-def gemm(A, W, M, N, K, *, out=None, out_dtype=None, lda=None, ldw=None, ldc=None, bias=None, gamma=None,
-         residual=None, ldr=None, act=ACT_NONE, taps=1, dil=1, stride=1, pad=0, t_in=None, t_out=None, alpha=1.0,
-         out_scale=1.0):
-    """C[M, N] = epi(A (*) W^T); see include/swc.h swc_gemm.  A: [.., lda], W: [N, ldw].
-    float16 tensors are split-f16 (2 halves per logical column); lda/ldw/ldc are LOGICAL columns."""
-    lib = _lib.load()
+def _gemm_args(A, W, M, N, K, *, out=None, out_dtype=None, lda=None, ldw=None, ldc=None, bias=None, gamma=None,
+               residual=None, ldr=None, act=ACT_NONE, taps=1, dil=1, stride=1, pad=0, t_in=None, t_out=None, alpha=1.0,
+               out_scale=1.0):
+    """the swc_gemm_args block of a gemm() call and its output tensor (allocated here when `out` is None)"""
     _chk(A, "gemm A"); _chk(W, "gemm W")
     if A.dtype != W.dtype:
         raise _lib.SwcError(f"gemm: A is {A.dtype} but W is {W.dtype}")
@@ -74,18 +72,55 @@ def gemm(A, W, M, N, K, *, out=None, out_dtype=None, lda=None, ldw=None, ldc=Non
     a.taps, a.dil, a.stride, a.pad = taps, dil, stride, pad
     a.t_in = M if t_in is None else t_in
     a.t_out = M if t_out is None else t_out
-    if M == 0:
-        return out
     a.a_dtype, a.c_dtype, a.act = _DT[A.dtype], _DT[out.dtype], act
     a.alpha, a.out_scale = alpha, out_scale
+    return a, out
+
+
+def gemm(A, W, M, N, K, **kw):
+    """C[M, N] = epi(A (*) W^T); see include/swc.h swc_gemm.  A: [.., lda], W: [N, ldw].
+    float16 tensors are split-f16 (2 halves per logical column); lda/ldw/ldc are LOGICAL columns.
+    Keywords: out, out_dtype, lda, ldw, ldc, bias, gamma, residual, ldr, act, taps, dil, stride, pad, t_in, t_out, alpha,
+    out_scale (_gemm_args)."""
+    lib = _lib.load()
+    a, out = _gemm_args(A, W, M, N, K, **kw)
+    if M == 0:
+        return out
     prof = PROFILER
     if prof is not None:
         prof.begin({torch.bfloat16: "gemm_bf16", torch.float16: "gemm_f16s", FP8_T: "gemm_fp8"}.get(A.dtype, "gemm_f32"),
-                   2.0 * M * N * K * taps)
+                   2.0 * M * N * K * a.taps)
     _lib.check(lib.swc_gemm(C.byref(a), _stream()), "swc_gemm")
     if prof is not None:
         prof.end()
     return out
+
+
+def gemm_call_plan(A, W, M, N, K, **kw):
+    """gemm_plan of the argument block gemm() would pass for the same call (same positional and keyword arguments; give `out`,
+    or an output is allocated): what that call launches, without launching it."""
+    return gemm_plan(_gemm_args(A, W, M, N, K, **kw)[0])
+
+
+def _plan_dict(st):
+    return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+
+def gemm_plan(args):
+    """What swc_gemm would launch for a filled _lib.GemmArgs, as a dict of the swc_gemm_plan_out fields (include/swc.h): tile,
+    waves, staging, epilogue body, tile counts, band, grid and slots.  Host arithmetic only: nothing is launched, no pointer is
+    dereferenced and no device is needed; refuses what swc_gemm refuses."""
+    out = _lib.GemmPlan()
+    _lib.check(_lib.load().swc_gemm_plan(C.byref(args), C.byref(out)), "swc_gemm_plan")
+    return _plan_dict(out)
+
+
+def dwconv7_ln_plan(B, T, C_, out_dtype=torch.float32):
+    """What swc_dwconv7_ln would launch, as a dict of the swc_dwconv7_ln_plan_out fields (include/swc.h): S, NK, FULL, nst,
+    nstrips, slots, per and grid.  Host arithmetic only."""
+    out = _lib.Dwconv7LnPlan()
+    _lib.check(_lib.load().swc_dwconv7_ln_plan(B, T, C_, _DT[out_dtype], C.byref(out)), "swc_dwconv7_ln_plan")
+    return _plan_dict(out)
 
 
 def attention(qkv, lens, B, T, H, out=None, out_dtype=None, row_start=None, rows=None):

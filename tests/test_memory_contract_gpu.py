@@ -217,6 +217,29 @@ def test_gemm_conv_taps(kind, cin, cout, k, stride, dil, pad, T, slack):
     same3(case)
 
 
+# ------------------------------------------------------------------- plan functions (host structs; run here because
+# tests/test_poison_cpu.py looks for the @covers of every include/swc.h output entry point in this module; no GPU is used)
+@covers("swc_gemm_plan", "swc_dwconv7_ln_plan")
+def test_plan_functions_write_their_host_struct_only():
+    """the plan functions are host arithmetic: they fill the caller's HOST struct and nothing around it, and follow none of the
+    device pointers of the argument block (placeholders here, which a dereference would fault on the host)"""
+    from simwhisper_codec_amd import _lib
+    lib = _lib.load()
+    a = _lib.GemmArgs()
+    a.A = a.W = a.C = 0x10000
+    a.M, a.N, a.K, a.lda, a.ldw, a.ldc = 70000, 512, 64, 64, 64, 512
+    a.taps = a.dil = a.stride = 1
+    a.t_in = a.t_out = a.M
+    a.a_dtype, a.c_dtype = _lib.BF16, _lib.F32
+    for struct, call in ((_lib.GemmPlan, lambda p: lib.swc_gemm_plan(C.byref(a), p)),
+                         (_lib.Dwconv7LnPlan, lambda p: lib.swc_dwconv7_ln_plan(3, 2750, 512, _lib.F32, p))):
+        n, band = C.sizeof(struct), 64
+        raw = (C.c_ubyte * (n + 2 * band))(*([0xA5] * (n + 2 * band)))
+        plan = struct.from_buffer(raw, band)
+        assert call(C.byref(plan)) == 0 and plan.grid > 0 and plan.slots >= plan.grid
+        assert bytes(raw[:band]) == bytes([0xA5] * band) and bytes(raw[band + n:]) == bytes([0xA5] * band)
+
+
 # ----------------------------------------------------------------------------------------------------------- attention
 def _qkv(ar, ops, mode, B, T, H, lens, seed):
     """[B, T, 3 H 64] in the operand type; rows t >= lens[b] are masked but READ (keys are masked by score, rows are computed):
