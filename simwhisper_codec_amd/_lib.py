@@ -115,6 +115,14 @@ CODES_SIGNATURES = {
     "swc_codes_unpack_batch": ([_P, _L, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P], C.c_int),
 }
 
+# include/swc_metrics.h (quality metrics), one to one: name -> (argtypes, restype).  A table of its own as well
+STOI_SHORT = 1e-5  # SWC_STOI_SHORT: d of a row with fewer than 30 STFT frames
+STOI_TILE = 16     # SWC_STOI_TILE
+METRICS_SIGNATURES = {
+    "swc_stoi_workspace_bytes": ([_I, _L, _I, _I], C.c_int64),
+    "swc_stoi": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -136,7 +144,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

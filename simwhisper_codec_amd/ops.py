@@ -335,12 +335,34 @@ def f32_to_pcm16(x):
 _RESAMPLE_TABLES = {}
 
 
-def resample_table(orig_freq, new_freq, device):
+def pack_resample_table(K, orig, new, width, device):
+    """A filter table K f32 [new, 2 width + orig] (the layout of wavio.resample_taps, any filter: a caller's own design) ->
+    the packed form swc_resample takes: dict(orig, new, width, run, taps [new, run] f32, start [new] int32 (both on the
+    device), nnz = the largest count of non-zero taps of a phase).  Per phase the window of `run` taps that holds every
+    non-zero one is kept (taps outside it are exact zeros)."""
+    taps = K.shape[1]
+    if K.dtype != torch.float32 or K.dim() != 2 or K.shape[0] != new or taps != 2 * width + orig:
+        raise _lib.SwcError("resample table: K must be f32 [new, 2 width + orig]")
+    nz = K != 0
+    pos = torch.arange(taps)
+    first = torch.where(nz, pos, taps).amin(dim=1)
+    last = torch.where(nz, pos, -1).amax(dim=1)
+    run = max(int((last - first).max()) + 1, 1)
+    start = first.clamp(max=taps - run).clamp(min=0)
+    packed = torch.gather(K, 1, start[:, None] + torch.arange(run)[None, :])
+    return {"orig": orig, "new": new, "width": width, "run": run, "nnz": int(nz.sum(dim=1).max()),
+            "taps": packed.contiguous().to(device), "start": start.to(torch.int32).to(device)}
+
+
+def resample_table(orig_freq, new_freq, device, taps=None):
     """The packed filter table of swc_resample for one pair of rates on one device, built once and kept:
     -> dict(orig, new, width, run, taps [new, run] f32, start [new] int32 (both on the device), nnz = the largest count of
     non-zero taps of a phase).  The values are wavio.resample_taps' own f32 numbers; per phase the window of `run` taps that
-    holds every non-zero one is kept (taps outside it are exact zeros).  Equal rates give the 1-tap identity filter."""
+    holds every non-zero one is kept (taps outside it are exact zeros).  Equal rates give the 1-tap identity filter.
+    taps: a caller's own (K, orig, new, width) in the layout of wavio.resample_taps instead (packed, not kept)."""
     device = torch.device(device)
+    if taps is not None:
+        return pack_resample_table(*taps, device)
     key = (int(orig_freq), int(new_freq), device.type, device.index)
     hit = _RESAMPLE_TABLES.get(key)
     if hit is not None:
@@ -350,16 +372,7 @@ def resample_table(orig_freq, new_freq, device):
         K, orig, new, width = torch.ones(1, 1, dtype=torch.float32), 1, 1, 0
     else:
         K, orig, new, width = wavio.resample_taps(orig_freq, new_freq)
-    taps = K.shape[1]
-    nz = K != 0
-    pos = torch.arange(taps)
-    first = torch.where(nz, pos, taps).amin(dim=1)
-    last = torch.where(nz, pos, -1).amax(dim=1)
-    run = max(int((last - first).max()) + 1, 1)
-    start = first.clamp(max=taps - run).clamp(min=0)
-    packed = torch.gather(K, 1, start[:, None] + torch.arange(run)[None, :])
-    t = {"orig": orig, "new": new, "width": width, "run": run, "nnz": int(nz.sum(dim=1).max()),
-         "taps": packed.contiguous().to(device), "start": start.to(torch.int32).to(device)}
+    t = pack_resample_table(K, orig, new, width, device)
     _RESAMPLE_TABLES[key] = t
     return t
 
@@ -369,11 +382,12 @@ def resample_out_len(n_in, orig_freq, new_freq):
     return int(_lib.load().swc_resample_out_len(int(n_in), int(orig_freq), int(new_freq)))
 
 
-def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None):
+def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None, table=None):
     """Sample-rate conversion of a ragged batch in one launch (include/swc_audio.h swc_resample): rows = device tensors, all f32
     1-D (mono) or all int16, [n, channels] or flat interleaved -> (out [B, cols] f32: row b holds its ceil(new n_b / orig)
     samples and zeros behind them, the list of those lengths).  cols defaults to the longest output; a row longer than cols
-    is cut.  `out` (tests): an f32 device view [B, cols] with unit column stride to write into instead."""
+    is cut.  `out` (tests): an f32 device view [B, cols] with unit column stride to write into instead.  `table`: a packed
+    table of the caller's own filter (pack_resample_table) instead of the default one of the two rates."""
     lib = _lib.load()
     B = len(rows)
     if B == 0:
@@ -391,7 +405,7 @@ def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None):
             raise _lib.SwcError("resample: f32 rows are 1-D mono; int16 rows hold whole frames of `channels` samples")
         n_in.append(r.numel() // ch)
     device = rows[0].device
-    t = resample_table(orig_freq, new_freq, device)
+    t = resample_table(orig_freq, new_freq, device) if table is None else table
     n_out = [-(-t["new"] * n // t["orig"]) for n in n_in]
     if out is None:
         cols = max(n_out) if cols is None else int(cols)
@@ -409,6 +423,64 @@ def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None):
                                 t["width"], _ptr(t["taps"]), _ptr(t["start"]), t["run"], _ptr(out), ld, cols, B, _stream()),
                "swc_resample")
     return out, n_out
+
+
+def stoi_workspace_bytes(B, max_n_in, orig, new):
+    """swc_stoi_workspace_bytes of include/swc_metrics.h"""
+    v = int(_lib.load().swc_stoi_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))
+    if v < 0:
+        raise _lib.SwcError(f"stoi: no workspace size for B={B}, max_n_in={max_n_in}, rates {orig}:{new}")
+    return v
+
+
+def stoi_workspace_layout(B, max_n_in, orig, new):
+    """Where swc_stoi keeps what inside its workspace (csrc/swc_stoi.hip `layout`; for tests and debugging, not part of the
+    C-ABI): -> dict(n10max, ld10, Fmax, Mmax, byte offsets x10, y10, e, src, K, Xt, Yt, total).  x10 / y10 [B][ld10] f32 (absent
+    at 10 kHz), e [B][Fmax] f32 frame energies, src [B][Fmax] int32 kept frames, K [B] int32 their counts, Xt / Yt [B][15][Mmax]."""
+    up = lambda v: (v + 255) & ~255
+    n10 = max_n_in if orig == new else -(-max_n_in * new // orig)
+    L = {"n10max": n10, "ld10": (n10 + 3) & ~3, "Fmax": (n10 - 256) // 128 + 1 if n10 >= 256 else 0}
+    L["Mmax"] = max(L["Fmax"] - 1, 0)
+    o = 0
+    for name, size in (("x10", 0 if orig == new else B * L["ld10"] * 4), ("y10", 0 if orig == new else B * L["ld10"] * 4),
+                       ("e", B * L["Fmax"] * 4), ("src", B * L["Fmax"] * 4), ("K", B * 4), ("Xt", B * 15 * L["Mmax"] * 4),
+                       ("Yt", B * 15 * L["Mmax"] * 4)):
+        L[name] = o
+        o += up(size)
+    L["total"] = o
+    return L
+
+
+def stoi(x_rows, y_rows, table, max_n_in=None, d=None, segs=None, workspace=None):
+    """STOI of a ragged batch in one call (include/swc_metrics.h swc_stoi): x_rows / y_rows = lists of 1-D f32 device tensors,
+    pair b of equal length, `table` the packed 10 kHz filter (metrics.stoi_table) -> (d f32 [B], segs int32 [B]).
+    One upload of the row table, one workspace from torch.  max_n_in, d, segs, workspace (tests): the host's length bound,
+    the two outputs and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    B = len(x_rows)
+    if B == 0 or len(y_rows) != B:
+        raise _lib.SwcError(f"stoi: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
+    n_in = []
+    for x, y in zip(x_rows, y_rows):
+        _chk(x, "stoi clean row", torch.float32); _chk(y, "stoi degraded row", torch.float32)
+        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
+            raise _lib.SwcError("stoi: a pair is two contiguous 1-D rows of one length")
+        n_in.append(x.numel())
+    device = x_rows[0].device
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    need = stoi_workspace_bytes(B, max_n, table["orig"], table["new"])
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    d = torch.empty(B, device=device, dtype=torch.float32) if d is None else _chk(d, "stoi d", torch.float32)
+    segs = torch.empty(B, device=device, dtype=torch.int32) if segs is None else _chk(segs, "stoi segs", torch.int32)
+    _chk(workspace, "stoi workspace", torch.uint8)
+    if d.numel() != B or segs.numel() != B or not d.is_contiguous() or not segs.is_contiguous() or not workspace.is_contiguous():
+        raise _lib.SwcError("stoi: d and segs are contiguous [B], the workspace contiguous bytes")
+    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_stoi(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, table["orig"], table["new"], table["width"],
+                            _ptr(table["taps"]), _ptr(table["start"]), table["run"], _ptr(d), _ptr(segs), _ptr(workspace),
+                            workspace.numel(), B, _stream()), "swc_stoi")
+    return d, segs
 
 
 def set_saturation_counter(counters):

@@ -1,0 +1,84 @@
+"""Mean STOI of a directory of reconstructions against the directory of originals, on the GPU (metrics.stoi):
+
+    python tools/evaluate_stoi.py --original_dir A --synthesized_dir B [--sample_rate 16000] [--batch_size 32] [--verbose]
+
+Files are paired by sorted name (.wav / .flac), read through wavio (first channel, clamped to [-1, 1], brought to
+--sample_rate on the host if the file is at another rate), cut to the shorter of the two, and scored in batches.  Pairs too
+short to score (segs == 0) are listed by name and left out of the mean.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    p.add_argument("--original_dir", required=True, help="directory of the original files")
+    p.add_argument("--synthesized_dir", required=True, help="directory of the reconstructed files (same names)")
+    p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (8, 10, 16, 24, 32 or 48 kHz)")
+    p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_stoi call")
+    p.add_argument("--verbose", action="store_true", help="print every file's value")
+    return p
+
+
+def _audio_names(d):
+    return sorted(n for n in os.listdir(d) if n.lower().endswith((".wav", ".flac")))
+
+
+def pair_files(original_dir, synthesized_dir):
+    """pairs by sorted name; the two directories must hold the same number of audio files"""
+    a, b = _audio_names(original_dir), _audio_names(synthesized_dir)
+    if len(a) != len(b):
+        raise SystemExit(f"{original_dir} holds {len(a)} audio files, {synthesized_dir} {len(b)}")
+    return [(os.path.join(original_dir, x), os.path.join(synthesized_dir, y)) for x, y in zip(a, b)]
+
+
+def load_first_channel(path, sample_rate):
+    import numpy as np
+    import torch
+    from simwhisper_codec_amd import wavio
+    x, sr = wavio._read_flac(path) if path.lower().endswith(".flac") else wavio._read_wav(path)
+    w = torch.from_numpy(np.ascontiguousarray(x[:, 0], dtype=np.float32)).clamp_(-1.0, 1.0)
+    return w if int(sr) == int(sample_rate) else wavio.resample(w, int(sr), int(sample_rate))
+
+
+def summarise(names, d, segs):
+    """-> (mean over the pairs with segs > 0, or None; names of the pairs left out)"""
+    scored = [v for v, s in zip(d, segs) if s > 0]
+    skipped = [n for n, s in zip(names, segs) if s == 0]
+    return (sum(scored) / len(scored) if scored else None), skipped
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import torch
+    from simwhisper_codec_amd import metrics
+    pairs = pair_files(args.original_dir, args.synthesized_dir)
+    if not pairs:
+        raise SystemExit("no audio files")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    names, d, segs = [], [], []
+    for i in range(0, len(pairs), max(args.batch_size, 1)):
+        chunk = pairs[i:i + max(args.batch_size, 1)]
+        ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
+        deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        dv, sv = metrics.stoi(ref, deg, sample_rate=args.sample_rate, device=dev)
+        names += [os.path.basename(o) for o, _ in chunk]
+        d += [float(v) for v in dv.cpu()]
+        segs += [int(v) for v in sv.cpu()]
+    if args.verbose:
+        for n, v, s in zip(names, d, segs):
+            print(f"{n}: STOI {v:.3f} ({s} segments)" if s else f"{n}: too short to score")
+    mean, skipped = summarise(names, d, segs)
+    if skipped:
+        print(f"too short to score, left out of the mean ({len(skipped)}): " + ", ".join(skipped))
+    print(f"mean STOI: {mean:.3f} over {len(names) - len(skipped)} pairs" if mean is not None else "mean STOI: no pair long enough")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
