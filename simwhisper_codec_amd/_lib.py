@@ -123,6 +123,14 @@ METRICS_SIGNATURES = {
     "swc_stoi": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_quality.h (STOI + ESTOI + SI-SDR in one call), one to one: name -> (argtypes, restype).  The fourth table of its own
+ESTOI_GROUP = 4      # SWC_ESTOI_GROUP: segments (one wave each) per workgroup of the ESTOI segment kernel
+SISDR_CHUNK = 8192   # SWC_SISDR_CHUNK: samples per workgroup of the SI-SDR sum kernel
+QUALITY_SIGNATURES = {
+    "swc_quality_workspace_bytes": ([_I, _L, _I, _I], C.c_int64),
+    "swc_quality": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -144,7 +152,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -1,4 +1,4 @@
-"""Quality metrics on the GPU (include/swc_metrics.h).  The first one: STOI of a ragged batch of (clean, degraded) pairs,
+"""Quality metrics on the GPU (include/swc_metrics.h, include/swc_quality.h).  The first one: STOI of a ragged batch of (clean, degraded) pairs,
 the short-time objective intelligibility measure of Taal, Hendriks, Heusdens and Jensen (2011), non-extended form — what the
 reference's tools/base_eval/evaluate_model.py gets from `pystoi` one pair at a time on a host core.
 
@@ -6,6 +6,11 @@ reference's tools/base_eval/evaluate_model.py gets from `pystoi` one pair at a t
 
 The filter that brings the pair to 10 kHz is designed here in float64 (the Kaiser-windowed sinc of the published code,
 `resample_poly(x, p, q, window=h)`), rounded to f32 once and handed to the device resampler as a packed table.
+
+    q = metrics.quality(ref_list, deg_list, sample_rate=16000)      # {"stoi", "estoi", "si_sdr", "segs"}, one call
+
+adds ESTOI (Jensen and Taal 2016: STOI's front end, another last step) and SI-SDR (Le Roux et al. 2019: the scale-invariant
+waveform measure, on the samples as given); metrics.estoi and metrics.si_sdr are that call with one metric asked for.
 """
 import math
 
@@ -101,3 +106,56 @@ def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
                 o += rows[i].numel()
         rows = [r.to(device=device, dtype=torch.float32).contiguous() for r in rows]
         return ops.stoi(rows[0::2], rows[1::2], table)
+
+
+def _stage(ref_list, deg_list, device):
+    """the rows of stoi(): pair i cut to its shorter length, host rows staged in one upload -> (clean rows, degraded rows)"""
+    n = [min(int(x.numel()), int(y.numel())) for x, y in zip(ref_list, deg_list)]
+    rows = [t.reshape(-1)[:k] for pair, k in zip(zip(ref_list, deg_list), n) for t in pair]
+    host = [i for i, r in enumerate(rows) if r.device.type == "cpu"]
+    if host:
+        staged = torch.cat([rows[i].to(torch.float32) for i in host]).to(device, non_blocking=True)
+        o = 0
+        for i in host:
+            rows[i] = staged[o:o + rows[i].numel()]
+            o += rows[i].numel()
+    rows = [r.to(device=device, dtype=torch.float32).contiguous() for r in rows]
+    return rows[0::2], rows[1::2]
+
+
+def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS):
+    """STOI, ESTOI and SI-SDR of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_quality call: the lists, the cut
+    to the shorter length and the staging of host rows are those of stoi().  `want`: which of "stoi", "estoi", "si_sdr".
+    -> dict on `device`: a FloatTensor[B] per wanted metric and, when stoi or estoi is wanted, "segs" IntTensor[B] (a pair too
+    short for one segment has segs 0 and stoi = estoi = 1e-5).  si_sdr is in dB, at sample_rate as given (any rate: it needs
+    no 10 kHz filter), NaN for an empty pair.  Nothing is synchronised."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError("quality: the metrics are HIP kernels (there is no CPU fallback)")
+    want = tuple(want)
+    B = len(ref_list)
+    if len(deg_list) != B:
+        raise SwcError(f"quality: {B} reference and {len(deg_list)} degraded waveforms")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    front = "stoi" in want or "estoi" in want
+    if B == 0:
+        res = {w: torch.zeros(0, device=device) for w in want}
+        if front:
+            res["segs"] = torch.zeros(0, device=device, dtype=torch.int32)
+        return res
+    table = stoi_table(sample_rate, device) if front else None
+    with torch.cuda.device(device):
+        x_rows, y_rows = _stage(ref_list, deg_list, device)
+        return ops.quality(x_rows, y_rows, table, want=want)
+
+
+def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+    """ESTOI alone: -> (d FloatTensor[B], segs IntTensor[B]), the conventions of stoi()"""
+    r = quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("estoi",))
+    return r["estoi"], r["segs"]
+
+
+def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+    """SI-SDR alone, in dB: -> FloatTensor[B] (NaN for an empty pair).  sample_rate is not used by the measure: any rate works."""
+    return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",))["si_sdr"]

@@ -483,6 +483,83 @@ def stoi(x_rows, y_rows, table, max_n_in=None, d=None, segs=None, workspace=None
     return d, segs
 
 
+def quality_workspace_bytes(B, max_n_in, orig, new):
+    """swc_quality_workspace_bytes of include/swc_quality.h"""
+    v = int(_lib.load().swc_quality_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))
+    if v < 0:
+        raise _lib.SwcError(f"quality: no workspace size for B={B}, max_n_in={max_n_in}, rates {orig}:{new}")
+    return v
+
+
+def quality_workspace_layout(B, max_n_in, orig, new):
+    """Where swc_quality keeps what inside its workspace (csrc/swc_stoi.hip `qlayout`; for tests and debugging, not part of
+    the C-ABI): stoi_workspace_layout's entries at the same offsets, then Smax, chunks and the byte offsets eseg [B][Smax] f32
+    (ESTOI of every segment), rec [B][chunks][4] f64 (the SI-SDR partial sums of every chunk), stat [B][4] f64 (mx, my, alpha),
+    segs [B] int32 (used when the caller passes no segs), total."""
+    up = lambda v: (v + 255) & ~255
+    L = stoi_workspace_layout(B, max_n_in, orig, new)
+    L["Smax"] = max(L["Mmax"] - 29, 0)
+    L["chunks"] = -(-max_n_in // _lib.SISDR_CHUNK)
+    o = L["total"]
+    for name, size in (("eseg", B * L["Smax"] * 4), ("rec", B * L["chunks"] * 32), ("stat", B * 32), ("segs", B * 4)):
+        L[name] = o
+        o += up(size)
+    L["total"] = o
+    return L
+
+
+QUALITY_METRICS = ("stoi", "estoi", "si_sdr")
+
+
+def quality(x_rows, y_rows, table, want=QUALITY_METRICS, max_n_in=None, out=None, workspace=None):
+    """STOI, ESTOI and SI-SDR of a ragged batch in one call (include/swc_quality.h swc_quality): x_rows / y_rows = lists of 1-D
+    f32 device tensors, pair b of equal length, `table` the packed 10 kHz filter (metrics.stoi_table), `want` the metrics to
+    compute -> dict of the wanted f32 [B] tensors, and "segs" (int32 [B]) when stoi or estoi is among them.  With
+    want == ("si_sdr",) the table is not used and may be None.  One upload of the row table, one workspace from torch.
+    max_n_in, out, workspace (tests): the host's length bound, a dict of output tensors to write (stoi / estoi / si_sdr /
+    segs, any subset) and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    want = tuple(want)
+    if not want or any(w not in QUALITY_METRICS for w in want) or len(set(want)) != len(want):
+        raise _lib.SwcError(f"quality: want={want!r}: a non-empty choice of {QUALITY_METRICS}")
+    front = "stoi" in want or "estoi" in want
+    if front and table is None:
+        raise _lib.SwcError("quality: stoi and estoi need the 10 kHz table (metrics.stoi_table)")
+    B = len(x_rows)
+    if B == 0 or len(y_rows) != B:
+        raise _lib.SwcError(f"quality: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
+    n_in = []
+    for x, y in zip(x_rows, y_rows):
+        _chk(x, "quality clean row", torch.float32); _chk(y, "quality degraded row", torch.float32)
+        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
+            raise _lib.SwcError("quality: a pair is two contiguous 1-D rows of one length")
+        n_in.append(x.numel())
+    device = x_rows[0].device
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    t = table if front else {"orig": 1, "new": 1, "width": 0, "taps": None, "start": None, "run": 1}
+    need = quality_workspace_bytes(B, max_n, t["orig"], t["new"])
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    _chk(workspace, "quality workspace", torch.uint8)
+    out = dict(out or {})
+    res = {}
+    for name in want + (("segs",) if front else ()):
+        dtype = torch.int32 if name == "segs" else torch.float32
+        v = out.get(name)
+        v = torch.empty(B, device=device, dtype=dtype) if v is None else _chk(v, f"quality {name}", dtype)
+        if v.numel() != B or not v.is_contiguous():
+            raise _lib.SwcError(f"quality: {name} is a contiguous [B] tensor")
+        res[name] = v
+    if not workspace.is_contiguous():
+        raise _lib.SwcError("quality: the workspace is contiguous bytes")
+    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_quality(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, t["orig"], t["new"], t["width"],
+                               _ptr(t["taps"]), _ptr(t["start"]), t["run"], _ptr(res.get("stoi")), _ptr(res.get("estoi")),
+                               _ptr(res.get("segs")), _ptr(res.get("si_sdr")), _ptr(workspace), workspace.numel(), B, _stream()),
+               "swc_quality")
+    return res
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""
