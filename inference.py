@@ -40,7 +40,7 @@ sys.path.insert(0, ROOT)
 from audiocodec.model import AudioCodec  # noqa: E402
 from simwhisper_codec_amd import bitstream  # noqa: E402
 from simwhisper_codec_amd.pipeline import HostStager  # noqa: E402
-from simwhisper_codec_amd.wavio import find_audio_files, load_audio, read_pcm, read_pcm16, save_audio, save_pcm16  # noqa: E402
+from simwhisper_codec_amd.wavio import FlacRaw, find_audio_files, load_audio, read_flac_raw, read_pcm, read_pcm16, save_audio, save_pcm16  # noqa: E402
 
 
 def set_logging(level="INFO"):
@@ -77,13 +77,27 @@ def build_parser():
                         "16-bit PCM WAV crosses PCIe as it is and channel mean + sample-rate conversion run in one HIP kernel "
                         "(HostStager.to_device_pcm); other formats keep the host path.  The two sum in different orders: "
                         "outputs of such files differ in the last bits")
+    p.add_argument("--flac", type=str, default="host", choices=["host", "gpu"],
+                   help="where FLAC files are decoded.  host (default): on the loader threads (wavio.load_audio: entropy "
+                        "decode, both CRCs of every frame and the MD5 signature), every output as before.  gpu (needs a CUDA "
+                        "device; single-GPU --mode roundtrip / encode): a loader thread only finds the frames and checks "
+                        "their CRC-8, CRC-16 and the sample total, the compressed bytes of a batch cross PCIe as one copy and "
+                        "one HIP launch decodes every frame of every file (HostStager.to_device_flac); channel mean and "
+                        "sample-rate conversion of those files then run on the GPU whatever --resample says.  The MD5 "
+                        "signature is NOT checked on this path (it needs the decoded samples on the host).  Streams above "
+                        "16 bits, above 8 channels or with variable block size keep the host decoder")
     return p
 
 
-def load_file(path, target_rate, pcm16_ok, resample):
+def load_file(path, target_rate, pcm16_ok, resample, flac="host"):
     """What a loader thread reads from one file.  resample == "gpu": any PCM16 WAV as (int16 [n, ch], sample rate) for
     HostStager.to_device_pcm.  Else, with pcm16_ok, a mono PCM16 file at target_rate as its int16 samples (converted on the
-    GPU: the same values).  Everything else (other widths, channels, rates, FLAC) is decoded to f32 at target_rate here."""
+    GPU: the same values).  flac == "gpu" (with pcm16_ok): a FLAC file as wavio.FlacRaw, its bytes and frame table for
+    HostStager.to_device_flac.  Everything else (other widths, channels, rates, FLAC) is decoded to f32 at target_rate here."""
+    if pcm16_ok and flac == "gpu":
+        raw = read_flac_raw(path)
+        if raw is not None:
+            return raw
     if pcm16_ok and resample == "gpu":
         got = read_pcm(path)
         if got is not None:
@@ -95,8 +109,33 @@ def load_file(path, target_rate, pcm16_ok, resample):
     return load_audio(path, target_sample_rate=target_rate).reshape(-1)
 
 
-def stage_files(stager, loaded, device, target_rate):
-    """load_file's results of one batch -> f32 device tensors at target_rate (one host-to-device copy per sample format)"""
+def stage_files(stager, loaded, device, target_rate, deferred=None):
+    """load_file's results of one batch -> f32 device tensors at target_rate (one host-to-device copy per sample format).
+    FlacRaw items are decoded on the device; whether every frame decoded is known once the stream has been synchronised.
+    deferred: a list that receives one callable fix(out) for that moment — it replaces the entries of files with a failed
+    frame by load_audio's result (or raises load_audio's error, naming the file).  Without it the stream is synchronised and
+    the fix applied here."""
+    raws = [i for i, w in enumerate(loaded) if isinstance(w, FlacRaw)]
+    if raws:
+        out = [None] * len(loaded)
+        views, failed = stager.to_device_flac([loaded[i] for i in raws], device, target_rate)
+        for i, w in zip(raws, views):
+            out[i] = w
+        rest = [i for i in range(len(loaded)) if i not in raws]
+        if rest:
+            for i, w in zip(rest, stage_files(stager, [loaded[i] for i in rest], device, target_rate, deferred)):
+                out[i] = w
+
+        def fix(res):
+            for k in failed():
+                logging.warning(f"{loaded[raws[k]].path}: a frame failed to decode on the GPU; decoding the file on the host")
+                res[raws[k]] = load_audio(loaded[raws[k]].path, target_sample_rate=target_rate).reshape(-1).to(device)
+        if deferred is not None:
+            deferred.append(fix)
+        else:
+            torch.cuda.current_stream(device).synchronize()
+            fix(out)
+        return out
     pcm = [i for i, w in enumerate(loaded) if isinstance(w, tuple)]
     if pcm:  # --resample gpu
         out = [None] * len(loaded)
@@ -132,9 +171,14 @@ def main(argv=None):
     if world > 1 and args.mode != "roundtrip":
         raise SystemExit(f"--mode {args.mode} runs on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
                          "only --mode roundtrip is data-parallel")
+    if world > 1 and args.flac != "host":
+        raise SystemExit(f"--flac {args.flac} stages on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
+                         "data-parallel runs decode FLAC on the host")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    if args.flac == "gpu" and device.type != "cuda":
+        raise SystemExit("--flac gpu decodes FLAC files on the GPU: --device must be a CUDA device")
     if args.mode != "roundtrip" and device.type != "cuda":
         raise SystemExit(f"--mode {args.mode} packs and unpacks the codes on the GPU: --device must be a CUDA device")
     generator = load_model(args, device)
@@ -154,7 +198,7 @@ def main(argv=None):
     on_gpu = device.type == "cuda"
 
     def load_one(path):
-        return load_file(path, generator.input_sample_rate, on_gpu, args.resample)
+        return load_file(path, generator.input_sample_rate, on_gpu, args.resample, args.flac)
 
     def save_one(item):
         path, wav = item
@@ -169,10 +213,10 @@ def main(argv=None):
         with open(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ".swc"), "wb") as f:
             f.write(image.numpy())
 
-    def stage_in(cpu_wavs):
+    def stage_in(cpu_wavs, deferred):
         if not on_gpu:
             return cpu_wavs
-        return stage_files(stager, cpu_wavs, device, generator.input_sample_rate)
+        return stage_files(stager, cpu_wavs, device, generator.input_sample_rate, deferred)
 
     # wall seconds per stage, summed over the threads that run them (they overlap).  The launch threads (process) do nothing but
     # launch: reading + staging runs in the loader thread, the device -> host copy + writing in the saver thread
@@ -185,9 +229,12 @@ def main(argv=None):
 
     def load(paths):
         t = time.perf_counter()
-        wavs = stage_in(list(io.map(load_one, paths)))
+        deferred = []
+        wavs = stage_in(list(io.map(load_one, paths)), deferred)
         if on_gpu:
             torch.cuda.current_stream(device).synchronize()   # the staging buffer is re-used by the next batch
+            for fix in deferred:                              # --flac gpu: the frames' status words are on the host now
+                fix(wavs)
         account("load+h2d", time.perf_counter() - t)
         return wavs
 

@@ -131,6 +131,40 @@ QUALITY_SIGNATURES = {
     "swc_quality": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_flac.h (FLAC on the device path), one to one.  The fifth table of its own — and the one header whose
+# declarations live in two libraries: the decode calls here in libswc_hip.so, the host index in libswc_io.so (wavio binds it)
+class FlacFrame(C.Structure):
+    """swc_flac_frame"""
+    _fields_ = [("byte_off", C.c_int64), ("first_sample", C.c_int64), ("n_bytes", C.c_int32), ("blocksize", C.c_int32),
+                ("file", C.c_int32), ("hdr_bytes", C.c_int32), ("chan_assign", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FlacFile(C.Structure):
+    """swc_flac_file"""
+    _fields_ = [("out_off", C.c_int64), ("n_samples", C.c_int64), ("plane_off", C.c_int64), ("first_frame", C.c_int32),
+                ("n_frames", C.c_int32), ("channels", C.c_int32), ("bps", C.c_int32), ("blocksize", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class FlacStream(C.Structure):
+    """swc_flac_stream"""
+    _fields_ = [("total", C.c_int64), ("first_frame", C.c_int64), ("rate", C.c_int32), ("channels", C.c_int32),
+                ("bps", C.c_int32), ("blocksize", C.c_int32)]
+
+
+FLAC_E_HOSTONLY = -6      # SWC_FLAC_E_HOSTONLY
+FLAC_PLANE_ALIGN = 64     # SWC_FLAC_PLANE_ALIGN
+FLAC_ST = {0: "ok", 1: "table entry dropped", 2: "reserved code", 3: "order inconsistent with the block size",
+           4: "frame length", 5: "truncated", 6: "sample out of range"}   # SWC_FLAC_ST_*
+FLAC_SIGNATURES = {
+    "swc_flac_decode_workspace_bytes": ([C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, C.POINTER(C.c_int64)], C.c_int64),
+    "swc_flac_decode_batch": ([_P, _L, _P, _I, _P, _I, _P, _L, _P, _P, _L, _P], C.c_int),
+    "swc_flac_decode_batch_ex": ([_P, _L, _P, _I, _P, _I, _P, _L, _P, _P, _L, _I, _P], C.c_int),
+}
+FLAC_IO_SIGNATURES = {
+    "swc_flac_index": ([C.c_char_p, C.c_size_t, _L, C.POINTER(FlacStream), _P, _L], C.c_int64),
+}
+
 _lib = None
 
 
@@ -152,7 +186,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libswc_hip.so")
 SOURCES = ["swc_api.hip", "swc_gemm.hip", "swc_attention.hip", "swc_attention16.hip", "swc_pointwise.hip", "swc_convnext.hip", "swc_mlp.hip", "swc_convnext64.hip", "swc_projln.hip",
-           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip"]
+           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip"]
 ARCH = "gfx950"
 # per-file flags.  -fno-slp-vectorize: hipcc otherwise packs adjacent f32 mul/add/fma into v_pk_*_f32, which issue at
 # half rate on gfx950 and cost extra v_mov shuffles — slower beside MFMAs (softmax, epilogues)
@@ -39,7 +39,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -87,18 +87,62 @@ IO_SOURCES = ["swc_flac.c"]
 def build_io_library(force=False):
     """Host-side helper library (plain C, gcc): the FLAC decoder behind wavio.load_audio.  No GPU code, no dependency."""
     srcs = [os.path.join(CSRC, f) for f in IO_SOURCES]
-    if not force and os.path.exists(IO_LIB_PATH) and all(os.path.getmtime(f) <= os.path.getmtime(IO_LIB_PATH) for f in srcs):
+    deps = srcs + [os.path.join(ROOT, "include", "swc_flac.h")]
+    if not force and os.path.exists(IO_LIB_PATH) and all(os.path.getmtime(f) <= os.path.getmtime(IO_LIB_PATH) for f in deps):
         return IO_LIB_PATH
     cc = next((c for c in (os.environ.get("CC"), shutil.which("gcc"), shutil.which("cc"), shutil.which("clang")) if c), None)
     if cc is None:
         raise RuntimeError("no C compiler found for libswc_io.so (set CC)")
     tmp = IO_LIB_PATH + ".tmp"
-    r = subprocess.run([cc, "-O2", "-std=c99", "-Wall", "-shared", "-fPIC", "-o", tmp] + srcs,
+    r = subprocess.run([cc, "-O2", "-std=c99", "-Wall", "-I", os.path.join(ROOT, "include"), "-shared", "-fPIC", "-o", tmp] + srcs,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"building libswc_io.so failed:\n{r.stdout}")
     os.replace(tmp, IO_LIB_PATH)
     return IO_LIB_PATH
+
+
+FLAC_CHECK_PATH = os.path.join(HERE, "swc_flac_check")
+FLAC_CHECK_SOURCES = ["swc_flac_check.cpp", "swc_flac.c"]
+
+
+def build_flac_check(force=False, sanitize=True):
+    """swc_flac_check: a stand-alone host program (its own main) that runs the shared frame decoder csrc/swc_flac_frame.h —
+    the text the GPU kernel runs — over FLAC streams given on its command line, indexed by swc_flac_index, and compares with
+    swc_flac_decode.  Compiled with -fsanitize=address,undefined: an out-of-bounds read or write of the decoder shows up here,
+    on the host, before anything runs on a GPU (tests/test_flac_frame_cpu.py).  No GPU code, nothing preloaded.
+    sanitize=False builds the same program without the sanitizers (swc_flac_check_plain): the host build whose per-frame
+    status words the GPU tests compare the kernel's with."""
+    srcs = [os.path.join(CSRC, f) for f in FLAC_CHECK_SOURCES]
+    deps = srcs + [os.path.join(CSRC, "swc_flac_frame.h"), os.path.join(ROOT, "include", "swc_flac.h")]
+    target = FLAC_CHECK_PATH if sanitize else FLAC_CHECK_PATH + "_plain"
+    if not force and os.path.exists(target) and all(os.path.getmtime(f) <= os.path.getmtime(target) for f in deps):
+        return target
+    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("g++"), shutil.which("clang++")) if c), None)
+    cc = next((c for c in (os.environ.get("CC"), shutil.which("gcc"), shutil.which("cc"), shutil.which("clang")) if c), None)
+    if cxx is None or cc is None:
+        raise RuntimeError("no C / C++ compiler found for swc_flac_check (set CC / CXX)")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"] if sanitize else ["-O2"]
+    tag = "san" if sanitize else "plain"
+    inc = ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    obj_c, obj_x = os.path.join(objdir, f"flac_check_io_{tag}.o"), os.path.join(objdir, f"flac_check_main_{tag}.o")
+    tmp = target + ".tmp"
+    # the sanitizer runtimes are linked INTO the program where the toolchain has them as archives (gcc: -static-lib*san; clang
+    # does so by default): a stand-alone binary that needs nothing preloaded and does not care what else is
+    static = ["-static-libasan", "-static-libubsan"] if sanitize else []
+    steps = [[cc, "-std=c99", "-Wall"] + san + inc + ["-c", srcs[1], "-o", obj_c],
+             [cxx, "-std=c++17", "-Wall"] + san + inc + ["-c", srcs[0], "-o", obj_x],
+             [cxx] + san + static + ["-o", tmp, obj_x, obj_c]]
+    for k, cmd in enumerate(steps):
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0 and k == 2 and static:
+            r = subprocess.run([cxx] + san + ["-o", tmp, obj_x, obj_c], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"building swc_flac_check failed:\n{r.stdout}")
+    os.replace(tmp, target)
+    return target
 
 
 def stamp_commit():

@@ -395,3 +395,116 @@ int64_t swc_flac_decode(const uint8_t* data, size_t n, int32_t* out, int64_t cap
  * less than ... nothing safe exists in general, so the caller grows the buffer on FLAC_E_SPACE; this helper just offers
  * a first guess from the file size (verbatim 8-bit mono would be n samples) */
 int64_t swc_flac_max_samples(size_t n) { return (int64_t)n * 16 + 65536; }
+
+/* ---------------------------------------------------------------- frame index for the device path (include/swc_flac.h)
+ * No entropy decoding: the frames are found by their headers and PROVED by their CRCs, then decoded on the GPU
+ * (csrc/swc_flac_gpu.hip) one frame per work item. */
+#include "swc_flac.h"
+
+#define FLAC_E_HOSTONLY SWC_FLAC_E_HOSTONLY /* valid, but left to swc_flac_decode: > 16 bits, > 8 channels, variable block size */
+
+static uint8_t CRC8_TABLE[256];
+static uint16_t CRC16_TABLE[256];
+__attribute__((constructor)) static void crc_tables_init(void) { /* at load time, before any thread can call in */
+    for (int i = 0; i < 256; ++i) {
+        uint8_t b = (uint8_t)i;
+        CRC8_TABLE[i] = crc8(&b, 1);
+        CRC16_TABLE[i] = crc16(&b, 1);
+    }
+}
+
+typedef struct { int bs, ca, bps, hdr_len, variable; uint64_t number; } fhdr_t;
+
+/* the frame header at d[pos]: FLAC_OK, FLAC_E_FORMAT (no sync, cut, bad number coding), FLAC_E_UNSUP (reserved codes) or
+ * FLAC_E_CRC (its CRC-8) */
+static int parse_frame_header(const uint8_t* d, size_t n, size_t pos, fhdr_t* h) {
+    if (n - pos < 6 || d[pos] != 0xFF || (d[pos + 1] & 0xFE) != 0xF8) return FLAC_E_FORMAT;
+    h->variable = d[pos + 1] & 1;
+    const int bs_code = d[pos + 2] >> 4, sr_code = d[pos + 2] & 15;
+    h->ca = d[pos + 3] >> 4;
+    const int ss_code = (d[pos + 3] >> 1) & 7;
+    if (d[pos + 3] & 1) return FLAC_E_FORMAT;
+    size_t q = pos + 4;
+    const uint32_t lead = d[q++];
+    int ones = 0;
+    while (ones < 8 && (lead & (0x80u >> ones))) ++ones;
+    if (ones == 1 || ones == 8) return FLAC_E_FORMAT;
+    uint64_t v = ones ? (lead & (0x7Fu >> ones)) : lead;
+    for (int i = 1; i < ones; ++i) {
+        if (q >= n || (d[q] & 0xC0) != 0x80) return FLAC_E_FORMAT;
+        v = (v << 6) | (d[q++] & 0x3Fu);
+    }
+    h->number = v;
+    int bs = BS_TABLE[bs_code];
+    if (bs == 0 || sr_code == 15) return FLAC_E_UNSUP;
+    if (bs == -8) { if (q >= n) return FLAC_E_FORMAT; bs = d[q++] + 1; }
+    else if (bs == -16) { if (n - q < 2) return FLAC_E_FORMAT; bs = ((d[q] << 8) | d[q + 1]) + 1; q += 2; }
+    if (sr_code == 12) q += 1;
+    else if (sr_code == 13 || sr_code == 14) q += 2;
+    if (q >= n) return FLAC_E_FORMAT;
+    if (BPS_TABLE[ss_code] < 0 || h->ca > 10) return FLAC_E_UNSUP;
+    uint8_t c = 0;
+    for (size_t i = pos; i < q; ++i) c = CRC8_TABLE[c ^ d[i]];
+    if (c != d[q]) return FLAC_E_CRC;
+    h->bs = bs;
+    h->bps = BPS_TABLE[ss_code];
+    h->hdr_len = (int)(q + 1 - pos);
+    return FLAC_OK;
+}
+
+int64_t swc_flac_index(const uint8_t* data, size_t n, int64_t max_samples, swc_flac_stream* info, swc_flac_frame* frames,
+                       int64_t cap) {
+    info_t st;
+    if (!data || !info || max_samples <= 0 || cap < 0 || (cap > 0 && !frames)) return FLAC_E_FORMAT;
+    int rc = parse_header(data, n, &st);
+    if (rc != FLAC_OK) return rc;
+    if (st.ch > SWC_FLAC_MAX_CHANNELS || st.bps > SWC_FLAC_MAX_BPS) return FLAC_E_HOSTONLY;
+    if (st.max_bs == 0) return FLAC_E_FORMAT;
+    if (st.min_bs != st.max_bs) return FLAC_E_HOSTONLY;
+    if (st.total > max_samples) return FLAC_E_SPACE;
+    int64_t count = 0, done = 0;
+    int short_seen = 0;
+    size_t pos = st.first_frame;
+    while (pos < n) {
+        fhdr_t h;
+        rc = parse_frame_header(data, n, pos, &h);
+        if (rc != FLAC_OK) return rc;
+        if (h.variable || short_seen || h.bs > st.max_bs) return FLAC_E_HOSTONLY; /* only the last block may be short */
+        if (h.number != (uint64_t)count) return FLAC_E_HOSTONLY; /* frame k carries the number k: a stream cut out of another does not */
+        const int nch = h.ca < 8 ? h.ca + 1 : 2;
+        if (nch != st.ch || (h.bps != 0 && h.bps != st.bps)) return FLAC_E_UNSUP;
+        short_seen = h.bs != st.max_bs;
+        /* the end: the first candidate behind at least one subframe byte and the CRC-16 whose header checks out, carries the
+         * next frame number and has the running CRC-16 of this frame in front of it; else the end of the data */
+        uint16_t crc = 0;
+        size_t upto = pos, end = n;
+        for (size_t q = pos + (size_t)h.hdr_len + 3; q + 2 <= n; ++q) {
+            if (data[q] != 0xFF || (data[q + 1] & 0xFE) != 0xF8) continue;
+            for (; upto < q - 2; ++upto) crc = (uint16_t)((crc << 8) ^ CRC16_TABLE[(crc >> 8) ^ data[upto]]);
+            if (crc != (uint16_t)((data[q - 2] << 8) | data[q - 1])) continue; /* a false sync inside the frame */
+            fhdr_t nx;
+            if (parse_frame_header(data, n, q, &nx) != FLAC_OK || nx.number != h.number + 1) continue;
+            end = q;
+            break;
+        }
+        if (end == n) {
+            if (n - pos < (size_t)h.hdr_len + 3) return FLAC_E_FORMAT;
+            for (; upto < n - 2; ++upto) crc = (uint16_t)((crc << 8) ^ CRC16_TABLE[(crc >> 8) ^ data[upto]]);
+            if (crc != (uint16_t)((data[n - 2] << 8) | data[n - 1])) return FLAC_E_CRC;
+        }
+        if (end - pos > SWC_FLAC_MAX_FRAME_BYTES) return FLAC_E_HOSTONLY;
+        done += h.bs;
+        if (done > max_samples || count >= SWC_FLAC_MAX_FRAMES) return FLAC_E_SPACE;
+        if (count < cap) {
+            swc_flac_frame* f = frames + count;
+            f->byte_off = (int64_t)pos; f->first_sample = done - h.bs; f->n_bytes = (int32_t)(end - pos); f->blocksize = h.bs;
+            f->file = 0; f->hdr_bytes = h.hdr_len; f->chan_assign = h.ca; f->reserved = 0;
+        }
+        ++count;
+        pos = end;
+    }
+    if (st.total && done != st.total) return FLAC_E_FORMAT;
+    info->total = done; info->first_frame = (int64_t)st.first_frame;
+    info->rate = st.sr; info->channels = st.ch; info->bps = st.bps; info->blocksize = st.max_bs;
+    return count;
+}

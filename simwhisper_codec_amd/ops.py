@@ -425,6 +425,55 @@ def resample(rows, orig_freq, new_freq, channels=1, cols=None, out=None, table=N
     return out, n_out
 
 
+def flac_workspace_layout(n_samples, channels):
+    """Where swc_flac_decode_batch keeps what inside its workspace (swc_flac_decode_workspace_bytes of include/swc_flac.h,
+    restated): file b's int32 planes [channels[b]][n_samples[b]] start at ELEMENT offset plane_off[b], each on a boundary of
+    _lib.FLAC_PLANE_ALIGN elements -> (plane_off list, total bytes)."""
+    A = _lib.FLAC_PLANE_ALIGN
+    offs, pos = [], 0
+    for n, ch in zip(n_samples, channels):
+        if n < 0 or not 1 <= ch <= 8:
+            raise _lib.SwcError(f"flac: no workspace for a file of {n} samples x {ch} channels")
+        offs.append(pos)
+        pos += (int(n) * int(ch) + A - 1) // A * A
+    return offs, pos * 4
+
+
+def flac_workspace_bytes(n_samples, channels):
+    """swc_flac_decode_workspace_bytes itself -> (plane_off list, total bytes)"""
+    B = len(n_samples)
+    ns, cs, po = (C.c_int64 * max(B, 1))(*n_samples), (C.c_int32 * max(B, 1))(*channels), (C.c_int64 * max(B, 1))()
+    v = int(_lib.load().swc_flac_decode_workspace_bytes(ns, cs, B, po))
+    if v < 0:
+        raise _lib.SwcError(f"flac: no workspace size for n_samples={list(n_samples)}, channels={list(channels)}")
+    return list(po)[:B], v
+
+
+def flac_decode(data, frames, files, out, status, workspace, n_frames=None, B=None, frames_per_wave=0):
+    """The FLAC frames of a batch of files -> interleaved int16 samples (include/swc_flac.h swc_flac_decode_batch; two launches
+    on the current stream, nothing else).  All device tensors: data uint8 (the compressed bytes), frames / files uint8 views
+    of the swc_flac_frame / swc_flac_file tables, out int16, status int32 [n_frames] (every word is written: 0 or a
+    SWC_FLAC_ST_* code), workspace uint8 of flac_workspace_layout's size, 16-byte aligned.  Only the files' own spans of
+    `out` are written, and only for files whose frames all have status 0.  frames_per_wave (tools/bench_flac.py): the frame
+    kernel's mapping, 0 = the library's choice; results do not depend on it."""
+    lib = _lib.load()
+    for t, name, dt in ((data, "data", torch.uint8), (frames, "frames", torch.uint8), (files, "files", torch.uint8),
+                        (out, "out", torch.int16), (status, "status", torch.int32), (workspace, "workspace", torch.uint8)):
+        _chk(t, f"flac_decode {name}", dt)
+        if not t.is_contiguous():
+            raise _lib.SwcError(f"flac_decode: {name} must be contiguous")
+    fsz, isz = C.sizeof(_lib.FlacFrame), C.sizeof(_lib.FlacFile)
+    n_frames = frames.numel() // fsz if n_frames is None else int(n_frames)
+    B = files.numel() // isz if B is None else int(B)
+    if n_frames * fsz > frames.numel() or B * isz > files.numel() or status.numel() < n_frames:
+        raise _lib.SwcError(f"flac_decode: tables of {frames.numel()} / {files.numel()} bytes and {status.numel()} status words "
+                            f"for {n_frames} frames of {B} files")
+    _lib.check(lib.swc_flac_decode_batch_ex(_ptr(data), data.numel(), _ptr(frames), n_frames, _ptr(files), B, _ptr(out), out.numel(),
+                                            _ptr(status), _ptr(workspace), workspace.numel(), int(frames_per_wave), _stream()),
+               "swc_flac_decode_batch")
+    return out, status
+
+
 def stoi_workspace_bytes(B, max_n_in, orig, new):
     """swc_stoi_workspace_bytes of include/swc_metrics.h"""
     v = int(_lib.load().swc_stoi_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))

@@ -125,23 +125,11 @@ class HostStager:
         one swc_resample launch per distinct (rate, channels) among the items that are not already mono at target_rate
         (channel mean, scaling and filter in that kernel) and one swc_pcm16_to_f32 over the others: for those the values
         are to_device_pcm16's, bit for bit."""
-        from . import ops
         target_rate = int(target_rate)
         pcm = [t if t.dim() == 2 else t.reshape(-1, 1) for t, _ in items]
-        lens = [int(t.numel()) for t in pcm]
-        plain = [i for i, (t, (_, sr)) in enumerate(zip(pcm, items)) if t.shape[1] == 1 and int(sr) == target_rate]
-        groups = {}
-        for i, (t, (_, sr)) in enumerate(zip(pcm, items)):
-            if i not in plain:
-                groups.setdefault((int(sr), int(t.shape[1])), []).append(i)
         # the plain items first, back to back on 16-byte boundaries (one conversion over their span), the others behind
-        offs, pos, n_plain = [0] * len(pcm), 0, 0
-        for k, i in enumerate(plain + [i for idx in groups.values() for i in idx]):
-            offs[i] = pos
-            pos += (lens[i] + 7) // 8 * 8
-            if k + 1 == len(plain):
-                n_plain = pos
-        out = [None] * len(pcm)
+        offs, pos, lens, plain, n_plain, groups = self._pcm_layout(
+            [(int(t.shape[0]), int(t.shape[1]), int(sr)) for t, (_, sr) in zip(pcm, items)], target_rate)
         if pos == 0:
             return [torch.empty(0, dtype=torch.float32, device=device) for _ in pcm]
         buf = getattr(self._tls, "buf16", None)
@@ -152,6 +140,34 @@ class HostStager:
             buf[o:o + n].copy_(t.reshape(-1))
         dev16 = torch.empty(pos, dtype=torch.int16, device=device)
         dev16.copy_(buf[:pos], non_blocking=True)
+        return self._pcm_to_f32(dev16, offs, lens, plain, n_plain, groups, device, target_rate)
+
+    @staticmethod
+    def _pcm_layout(shapes, target_rate):
+        """[(samples per channel, channels, rate)] -> (element offsets in the int16 device buffer, its size, lens, plain, n_plain,
+        groups): the items that are mono at target_rate (`plain`) first, back to back on 16-byte boundaries, n_plain elements
+        in all (one conversion over their span), the others behind, grouped by (rate, channels)."""
+        lens = [n * ch for n, ch, _ in shapes]
+        plain = [i for i, (_, ch, sr) in enumerate(shapes) if ch == 1 and sr == target_rate]
+        groups = {}
+        for i, (_, ch, sr) in enumerate(shapes):
+            if i not in plain:
+                groups.setdefault((sr, ch), []).append(i)
+        offs, pos, n_plain = [0] * len(shapes), 0, 0
+        for k, i in enumerate(plain + [i for idx in groups.values() for i in idx]):
+            offs[i] = pos
+            pos += (lens[i] + 7) // 8 * 8
+            if k + 1 == len(plain):
+                n_plain = pos
+        return offs, pos, lens, plain, n_plain, groups
+
+    @staticmethod
+    def _pcm_to_f32(dev16, offs, lens, plain, n_plain, groups, device, target_rate):
+        """the back half of to_device_pcm and to_device_flac: interleaved int16 samples on the device, laid out by
+        _pcm_layout -> f32 mono views at target_rate (one swc_pcm16_to_f32 over the plain span, one swc_resample per
+        (rate, channels) group)"""
+        from . import ops
+        out = [None] * len(offs)
         with torch.cuda.device(device):
             if plain:
                 dev = ops.pcm16_to_f32(dev16[:n_plain])
@@ -162,6 +178,81 @@ class HostStager:
                 for k, i in enumerate(idx):
                     out[i] = y[k, : n_out[k]]
         return out
+
+    def _pinned(self, name, nbytes):
+        """this thread's pinned uint8 staging buffer `name`, grown on demand"""
+        buf = getattr(self._tls, name, None)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
+            setattr(self._tls, name, buf)
+        return buf
+
+    def to_device_flac(self, items, device, target_rate, frames_per_wave=0, events=None):
+        """items = wavio.FlacRaw (read_flac_raw) -> (f32 mono device views at target_rate, failed).  The files' compressed bytes
+        are packed into a pinned byte buffer and cross PCIe as ONE copy, the frame and file tables as one more; one
+        swc_flac_decode_batch decodes every frame of every file into an int16 device buffer laid out as to_device_pcm lays
+        out its own (mono files at target_rate first, 16-byte boundaries), and the same back half follows: swc_pcm16_to_f32
+        over the plain span, swc_resample per (rate, channels).  Files below 16 bits are shifted up to 16 (the value
+        load_audio gives: sample * 2^-(bits-1)).
+        failed(): call it once the stream has been synchronised -> the indices of the items of which a frame reported a
+        non-zero status (their views hold no audio: the caller redoes them through wavio.load_audio, which raises its usual
+        error naming the file, or succeeds).  The status words travel to pinned memory behind the decode: no further wait.
+        frames_per_wave, events (tools/bench_flac.py): the frame kernel's mapping (0 = the library's choice) and a pair of
+        timing events recorded on the current stream right in front of and behind the decode call."""
+        import numpy as np
+        from . import _lib, ops
+        target_rate = int(target_rate)
+        if not items:
+            return [], (lambda: [])
+        offs, pos, lens, plain, n_plain, groups = self._pcm_layout([(it.total, it.channels, it.rate) for it in items], target_rate)
+        plane_off, ws_bytes = ops.flac_workspace_layout([it.total for it in items], [it.channels for it in items])
+        nfr = [len(it.frames) for it in items]
+        n_frames = sum(nfr)
+        if pos == 0 or n_frames == 0:
+            return [torch.empty(0, dtype=torch.float32, device=device) for _ in items], (lambda: [])
+        # only the frames' bytes travel: [first frame, end of file) of every file, back to back (no alignment is needed)
+        starts = [int(it.frames["byte_off"][0]) if len(it.frames) else len(it.data) for it in items]
+        sizes = [len(it.data) - s for it, s in zip(items, starts)]
+        n_bytes = sum(sizes)
+        fdt, idt = np.dtype(_lib.FlacFrame), np.dtype(_lib.FlacFile)
+        tab_bytes = n_frames * fdt.itemsize + len(items) * idt.itemsize
+        buf8, tab = self._pinned("buf8", n_bytes), self._pinned("buftab", tab_bytes)
+        host8 = buf8.numpy()
+        frames = tab.numpy()[: n_frames * fdt.itemsize].view(fdt)
+        files = tab.numpy()[n_frames * fdt.itemsize: tab_bytes].view(idt)
+        b0 = f0 = 0
+        for i, it in enumerate(items):
+            host8[b0:b0 + sizes[i]] = it.data[starts[i]:]
+            fr = frames[f0:f0 + nfr[i]]
+            fr[:] = it.frames
+            fr["byte_off"] += b0 - starts[i]
+            fr["file"] = i
+            files[i] = (offs[i], it.total, plane_off[i], f0, nfr[i], it.channels, it.bps, it.blocksize, 0)
+            b0 += sizes[i]
+            f0 += nfr[i]
+        dev8 = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+        dev8.copy_(buf8[:n_bytes], non_blocking=True)
+        devtab = torch.empty(tab_bytes, dtype=torch.uint8, device=device)
+        devtab.copy_(tab[:tab_bytes], non_blocking=True)
+        dev16 = torch.empty(pos, dtype=torch.int16, device=device)
+        status = torch.empty(n_frames, dtype=torch.int32, device=device)
+        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            if events is not None:
+                events[0].record()
+            ops.flac_decode(dev8, devtab[: n_frames * fdt.itemsize], devtab[n_frames * fdt.itemsize:], dev16, status, workspace,
+                            n_frames=n_frames, B=len(items), frames_per_wave=frames_per_wave)
+            if events is not None:
+                events[1].record()
+        st_host = self._pinned("bufst", n_frames * 4)[: n_frames * 4].view(torch.int32)
+        st_host.copy_(status, non_blocking=True)
+        out = self._pcm_to_f32(dev16, offs, lens, plain, n_plain, groups, device, target_rate)
+        first = np.cumsum([0] + nfr)
+
+        def failed():
+            st = st_host.numpy()
+            return [i for i in range(len(items)) if st[first[i]:first[i + 1]].any()]
+        return out, failed
 
     def codes_to_host(self, codes_list):
         """encode()'s codes_list -> the utterances' SWC1 file images (bitstream.py) as host uint8 views of this thread's pinned

@@ -10,6 +10,11 @@ Conventions the reference leaves to torchaudio and which are therefore OUR choic
   * float -> PCM16: round(clip(x, -1, 1) * 32767);
   * FLAC integers are scaled by 2^-(bits-1), as torchaudio does; every decode checks both frame CRCs and the stream's
     MD5 signature and raises on a mismatch (no other FLAC decoder exists here to pin this one against).
+  * FLAC for the device path (`--flac gpu`): read_flac_raw does no entropy decoding — swc_flac_index (csrc/swc_flac.c)
+    finds every frame and checks its CRC-8, its CRC-16 and the sample total; the compressed bytes cross PCIe and
+    swc_flac_decode_batch (csrc/swc_flac_gpu.hip) decodes one frame per work item.  The MD5 signature is NOT checked on
+    that path (it needs the decoded samples on the host).  Streams above 16 bits, above 8 channels or with variable
+    block size stay with the host decoder.
 `.mp3` is listed (helpers.py:106) but cannot be decoded here: a clear error is raised.
 """
 import glob
@@ -93,6 +98,10 @@ def _io():
         lib.swc_flac_decode.restype = C.c_int64
         lib.swc_flac_max_samples.argtypes = [C.c_size_t]
         lib.swc_flac_max_samples.restype = C.c_int64
+        from . import _lib as L
+        for name, (argtypes, restype) in L.FLAC_IO_SIGNATURES.items():   # include/swc_flac.h, the host half
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
         _io_lib = lib
     return _io_lib
 
@@ -143,6 +152,78 @@ def _decode_flac(path):
     if not md5.value:
         logging.warning(f"{path}: the stream carries no MD5 signature; frame CRCs verified only")
     return out[:n], int(sr.value), int(bits.value)
+
+
+def _flac_ceiling(path, ch, sr, total):
+    """samples per channel one FLAC file may expand to, whatever its header says (FLAC_MAX_SAMPLES, SWC_FLAC_MAX_SECONDS):
+    the ceiling of _decode_flac, for the device path as well"""
+    hard = FLAC_MAX_SAMPLES // max(1, ch)
+    if os.environ.get("SWC_FLAC_MAX_SECONDS"):
+        hard = min(hard, int(float(os.environ["SWC_FLAC_MAX_SECONDS"]) * max(1, sr)))
+    if total and total > hard:
+        raise ValueError(f"{path}: STREAMINFO declares {total} samples per channel, more than the decoder's ceiling of "
+                         f"{hard} (FLAC_MAX_SAMPLES / SWC_FLAC_MAX_SECONDS)")
+    return max(1, hard)
+
+
+class FlacRaw:
+    """One FLAC file for the device path (read_flac_raw): its bytes as they are, and the table that lets the GPU decode every
+    frame on its own.  data: uint8 array, the whole file.  frames: structured array of swc_flac_frame records (byte_off within
+    data).  rate, channels, bps, blocksize, total: the stream's parameters, total = samples per channel."""
+    __slots__ = ("path", "data", "frames", "rate", "channels", "bps", "blocksize", "total")
+
+    def __init__(self, path, data, frames, info):
+        self.path, self.data, self.frames = path, data, frames
+        self.rate, self.channels, self.bps = int(info.rate), int(info.channels), int(info.bps)
+        self.blocksize, self.total = int(info.blocksize), int(info.total)
+
+    def __len__(self):
+        return self.total
+
+
+def flac_index(data, path="<bytes>", max_samples=None):
+    """swc_flac_index of include/swc_flac.h on a bytes-like -> (FlacStream, frames structured array), or the negative code.
+    No entropy decoding: frame headers, CRC-8, CRC-16 and the sample total are checked.  The record buffer is sized by the
+    length of the data (a frame is at least 9 bytes), never by what a header claims."""
+    import ctypes as C
+    from . import _lib as L
+    lib = _io()
+    data = bytes(data) if not isinstance(data, bytes) else data
+    sr, ch, bits, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.swc_flac_info(data, len(data), C.byref(sr), C.byref(ch), C.byref(bits), C.byref(total))
+    if rc != 0:
+        return rc
+    if max_samples is None:
+        max_samples = _flac_ceiling(path, ch.value, sr.value, int(total.value))
+    info = L.FlacStream()
+    dt = np.dtype(L.FlacFrame)
+    cap = max(16, len(data) // 256)
+    while True:
+        frames = np.zeros(cap, dtype=dt)
+        n = int(lib.swc_flac_index(data, len(data), int(max_samples), C.byref(info), frames.ctypes.data_as(C.c_void_p), cap))
+        if n < 0:
+            return n
+        if n <= cap:
+            return info, frames[:n]
+        cap = min(n, len(data) // 9 + 1)   # what the walk counted; a frame cannot take fewer than 9 bytes
+
+
+def read_flac_raw(path):
+    """A FLAC file for the device path (`inference.py --flac gpu`, HostStager.to_device_flac): -> FlacRaw (the file's bytes,
+    the stream's parameters, the frame table of swc_flac_index), or None when the stream is not for the device path — more
+    than 16 bits per sample, more than 8 channels, variable block size — or does not pass the index: the caller then uses
+    load_audio, which decodes it on the host or raises its usual error naming the file.  Nothing is entropy-decoded here and
+    the MD5 signature is NOT checked on this path (it needs the decoded samples on the host); both CRCs of every frame and
+    the sample total are."""
+    if os.path.splitext(path)[1].lower() != ".flac":
+        return None
+    with open(path, "rb") as f:
+        data = f.read()
+    got = flac_index(data, path)
+    if isinstance(got, int):
+        return None
+    info, frames = got
+    return FlacRaw(path, np.frombuffer(data, dtype=np.uint8), frames, info)
 
 
 def _pcm16_chunks(audio_path):
