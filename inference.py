@@ -86,6 +86,15 @@ def build_parser():
                         "sample-rate conversion of those files then run on the GPU whatever --resample says.  The MD5 "
                         "signature is NOT checked on this path (it needs the decoded samples on the host).  Streams above "
                         "16 bits, above 8 channels or with variable block size keep the host decoder")
+    p.add_argument("--output_format", type=str, default="wav", choices=["wav", "flac"],
+                   help="what --mode roundtrip / decode write.  wav (default): PCM16 WAV, every output as before.  flac (needs "
+                        "a CUDA device; single GPU): <basename>.flac, lossless and about half the bytes — the int16 samples "
+                        "are compressed on the GPU (HostStager.flac_to_host, swc_flac_encode_batch: fixed predictors, "
+                        "partitioned Rice coding, block size 4096) and only the compressed bytes cross PCIe")
+    p.add_argument("--flac_md5", type=str, default="device", choices=["device", "none"],
+                   help="the MD5 signature of --output_format flac files.  device (default): computed on the GPU, one lane "
+                        "per file (a serial chain: it can cost more than the compression itself).  none: the field stays "
+                        "zero, which FLAC defines as 'no signature'; decoders then skip that check")
     return p
 
 
@@ -174,9 +183,17 @@ def main(argv=None):
     if world > 1 and args.flac != "host":
         raise SystemExit(f"--flac {args.flac} stages on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
                          "data-parallel runs decode FLAC on the host")
+    if world > 1 and args.output_format != "wav":
+        raise SystemExit(f"--output_format {args.output_format} compresses on one GPU: start it without torch.distributed.run "
+                         f"(WORLD_SIZE={world}); data-parallel runs write WAV")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    flac_out = args.output_format == "flac"
+    if flac_out and device.type != "cuda":
+        raise SystemExit("--output_format flac compresses the output on the GPU: --device must be a CUDA device")
+    if flac_out and args.mode == "encode":
+        raise SystemExit("--output_format flac: --mode encode writes code files, no audio")
     if args.flac == "gpu" and device.type != "cuda":
         raise SystemExit("--flac gpu decodes FLAC files on the GPU: --device must be a CUDA device")
     if args.mode != "roundtrip" and device.type != "cuda":
@@ -208,10 +225,13 @@ def main(argv=None):
         else:
             save_audio(out, wav.reshape(1, -1), sample_rate=generator.output_sample_rate)
 
-    def save_image(item):
+    def save_image(item, ext=".swc"):
         path, image = item
-        with open(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ".swc"), "wb") as f:
+        with open(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ext), "wb") as f:
             f.write(image.numpy())
+
+    def save_flac(item):
+        save_image(item, ".flac")
 
     def stage_in(cpu_wavs, deferred):
         if not on_gpu:
@@ -242,6 +262,9 @@ def main(argv=None):
         t = time.perf_counter()
         if to_codes:   # wavs = bitstream.pack_batch's result: one copy into pinned memory, every file a slice of it
             list(io.map(save_image, zip(paths, bitstream.images_to_host(wavs))))
+        elif flac_out:   # wavs = pcm16_on_device's rows: compressed on the GPU, one copy of the file images into pinned memory
+            images = stager.flac_to_host(wavs, generator.output_sample_rate, md5=args.flac_md5 == "device")
+            list(io.map(save_flac, zip(paths, images)))
         else:
             host = stager.to_host(wavs) if on_gpu else wavs    # (the batch's stream was synchronised before it was handed back)
             list(io.map(save_one, zip(paths, host)))
@@ -328,7 +351,8 @@ def find_code_files(input_dir):
 
 
 def main_decode(args, generator, device):
-    """--mode decode: every *.swc of --input_dir -> <output_dir>/<basename>.wav (PCM16), --batch_size files per decode() call.
+    """--mode decode: every *.swc of --input_dir -> <output_dir>/<basename>.wav (PCM16; .flac with --output_format flac, see
+    HostStager.flac_to_host), --batch_size files per decode() call.
     Per batch: the files are read by the io threads and their headers checked on the host, their payloads cross PCIe as one
     copy and are unpacked by one launch, and nothing is decoded or written before every file of the batch has been found
     sound (a file that cannot be read, a bad header, a cut payload or code values outside the model's codebook stop the run
@@ -351,10 +375,16 @@ def main_decode(args, generator, device):
         bitstream.parse_header(data, path)
         return data
 
+    flac_out = args.output_format == "flac"
+
     def save_one(item):
         path, pcm = item
-        save_pcm16(os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0] + ".wav"), pcm,
-                   sample_rate=generator.output_sample_rate)
+        base = os.path.join(args.output_dir, os.path.splitext(os.path.basename(path))[0])
+        if flac_out:   # pcm = the file's image, a slice of the stager's pinned buffer
+            with open(base + ".flac", "wb") as f:
+                f.write(pcm.numpy())
+        else:
+            save_pcm16(base + ".wav", pcm, sample_rate=generator.output_sample_rate)
 
     total_audio, t0 = 0.0, time.perf_counter()
     with ThreadPoolExecutor(max_workers=max(1, args.io_threads)) as io, ThreadPoolExecutor(max_workers=2) as pool, torch.no_grad():
@@ -377,9 +407,17 @@ def main_decode(args, generator, device):
                                      "(a corrupt file, or codes of another model)")
                 logging.info(f"Successfully loaded {len(views)} code files with lengths {[v.shape[-1] for v in views]} frames")
                 syn = generator.decode(views, overlap_seconds=10, device=device)["syn_wav_list"]
-                host = stager.to_host(stager.pcm16_on_device(syn))
-            logging.info(f"Decoding completed, generated waveform lengths: {[len(w) for w in host]} samples")
-            total_audio += sum(len(w) for w in host) / generator.output_sample_rate
+                lens = [len(w) for w in syn]
+                if flac_out:
+                    if pending is not None:   # the images are slices of ONE pinned buffer: the last batch's are written first
+                        pending.result()
+                        pending = None
+                    host = stager.flac_to_host(stager.pcm16_on_device(syn), generator.output_sample_rate,
+                                               md5=args.flac_md5 == "device")
+                else:
+                    host = stager.to_host(stager.pcm16_on_device(syn))
+            logging.info(f"Decoding completed, generated waveform lengths: {lens} samples")
+            total_audio += sum(lens) / generator.output_sample_rate
             if pending is not None:
                 pending.result()
             pending = pool.submit(save, paths, host)

@@ -165,6 +165,12 @@ FLAC_IO_SIGNATURES = {
     "swc_flac_index": ([C.c_char_p, C.c_size_t, _L, C.POINTER(FlacStream), _P, _L], C.c_int64),
 }
 
+# include/swc_flac_enc.h (FLAC written on the device), one to one.  The sixth table of its own
+FLAC_ENC_SIGNATURES = {
+    "swc_flac_encode_workspace_bytes": ([C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int64)], C.c_int64),
+    "swc_flac_encode_batch": ([_P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _L, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -186,7 +192,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

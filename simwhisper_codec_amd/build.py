@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libswc_hip.so")
 SOURCES = ["swc_api.hip", "swc_gemm.hip", "swc_attention.hip", "swc_attention16.hip", "swc_pointwise.hip", "swc_convnext.hip", "swc_mlp.hip", "swc_convnext64.hip", "swc_projln.hip",
-           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip"]
+           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip"]
 ARCH = "gfx950"
 # per-file flags.  -fno-slp-vectorize: hipcc otherwise packs adjacent f32 mul/add/fma into v_pk_*_f32, which issue at
 # half rate on gfx950 and cost extra v_mov shuffles — slower beside MFMAs (softmax, epilogues)
@@ -39,7 +39,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -143,6 +143,31 @@ def build_flac_check(force=False, sanitize=True):
             raise RuntimeError(f"building swc_flac_check failed:\n{r.stdout}")
     os.replace(tmp, target)
     return target
+
+
+FLAC_ENC_CHECK_PATH = os.path.join(HERE, "swc_flac_enc_check")
+
+
+def build_flac_enc_check(force=False):
+    """swc_flac_enc_check: a stand-alone host program (its own main) over csrc/swc_flac_enc_bits.h — the MD5, CRC and header
+    code the FLAC encoder's kernels run — compiled with -fsanitize=address,undefined (tests/test_flac_enc_cpu.py).  No GPU code,
+    nothing preloaded."""
+    src = os.path.join(CSRC, "swc_flac_enc_check.cpp")
+    deps = [src, os.path.join(CSRC, "swc_flac_enc_bits.h"), os.path.join(ROOT, "include", "swc_flac_enc.h")]
+    if not force and os.path.exists(FLAC_ENC_CHECK_PATH) and all(os.path.getmtime(f) <= os.path.getmtime(FLAC_ENC_CHECK_PATH) for f in deps):
+        return FLAC_ENC_CHECK_PATH
+    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("g++"), shutil.which("clang++")) if c), None)
+    if cxx is None:
+        raise RuntimeError("no C++ compiler found for swc_flac_enc_check (set CXX)")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+    base = [cxx, "-std=c++17", "-Wall"] + san + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, src, "-o", FLAC_ENC_CHECK_PATH + ".tmp"]
+    r = subprocess.run(base + ["-static-libasan", "-static-libubsan"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:   # a toolchain without the runtimes as archives
+        r = subprocess.run(base, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"building swc_flac_enc_check failed:\n{r.stdout}")
+    os.replace(FLAC_ENC_CHECK_PATH + ".tmp", FLAC_ENC_CHECK_PATH)
+    return FLAC_ENC_CHECK_PATH
 
 
 def stamp_commit():

@@ -474,6 +474,75 @@ def flac_decode(data, frames, files, out, status, workspace, n_frames=None, B=No
     return out, status
 
 
+FLAC_ENC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
+FLAC_ENC_STREAM_HEADER, FLAC_ENC_MAX_HEADER = 42, 14   # SWC_FLAC_ENC_STREAM_HEADER, SWC_FLAC_ENC_MAX_HEADER
+
+
+def flac_encode_workspace_layout(n_samples, blocksize):
+    """swc_flac_encode_workspace_bytes of include/swc_flac_enc.h, restated -> (workspace bytes, out_cap): the workspace of a
+    call over len(n_samples) files of up to max(n_samples) samples (int64 frame offsets, int32 frame sizes, 16 MD5 bytes and
+    two int32 per file, the fixed-stride frame slots, each part on a 256-byte boundary) and the worst-case total output, every
+    frame VERBATIM under the longest header."""
+    B = len(n_samples)
+    if B > 65535 or blocksize not in FLAC_ENC_BLOCK_SIZES or any(n < 0 or n >= 1 << 31 for n in n_samples):
+        raise _lib.SwcError(f"flac_encode: no layout for {B} files, blocksize={blocksize}, n_samples={list(n_samples)[:8]}")
+    frames = lambda n: -(-int(n) // blocksize)   # noqa: E731
+    cap = sum(FLAC_ENC_STREAM_HEADER + frames(n) * (FLAC_ENC_MAX_HEADER + 1 + 2) + 2 * int(n) for n in n_samples if n > 0)
+    if B == 0:
+        return 0, cap
+    F = frames(max(n_samples))
+    if B * F > 1 << 24:
+        raise _lib.SwcError(f"flac_encode: {B * F} frames in one call (at most 2^24)")
+    slot = (FLAC_ENC_MAX_HEADER + 1 + 2 * blocksize + 2 + 15) // 16 * 16
+    return sum(-(-v // 256) * 256 for v in (8 * B * F, 4 * B * F, 16 * B, 8 * B, B * F * slot)), cap
+
+
+def flac_encode_workspace_bytes(n_samples, blocksize):
+    """swc_flac_encode_workspace_bytes itself -> (workspace bytes, out_cap)"""
+    B = len(n_samples)
+    ns, cap = (C.c_int64 * max(B, 1))(*n_samples), C.c_int64(0)
+    v = int(_lib.load().swc_flac_encode_workspace_bytes(ns, B, int(blocksize), C.byref(cap)))
+    if v < 0:
+        raise _lib.SwcError(f"flac_encode: no workspace size for blocksize={blocksize}, n_samples={list(n_samples)[:8]}")
+    return v, int(cap.value)
+
+
+def flac_encode(rows, rate, blocksize=4096, md5=True, max_n=None, out=None, workspace=None):
+    """Mono int16 device rows -> their complete .flac file images, back to back in one uint8 device buffer (include/swc_flac_enc.h
+    swc_flac_encode_batch: four or five launches on the current stream, nothing synchronises).  rows: 1-D int16 tensors (views
+    at any 2-byte alignment).  -> (buffer uint8, offsets int64 [B], sizes int64 [B]), the last two on the device: image b is
+    buffer[offsets[b] : offsets[b] + sizes[b]]; an empty row has size 0.  Nothing of the buffer behind the last image is
+    written.  md5=False leaves STREAMINFO's signature zero ("no signature") and skips the one-lane-per-file MD5 kernel.
+    max_n (default: the longest row), out, workspace (default: allocated here at flac_encode_workspace_layout's sizes for B
+    rows of max_n): what the tests vary; a file's bytes do not depend on them."""
+    lib = _lib.load()
+    B = len(rows)
+    for r in rows:
+        _chk(r, "flac_encode row", torch.int16)
+        if r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
+            raise _lib.SwcError("flac_encode: rows are 1-D contiguous int16 tensors")
+    lens = [int(r.numel()) for r in rows]
+    max_n = max(lens, default=0) if max_n is None else int(max_n)
+    ws_bytes, cap = flac_encode_workspace_layout([max_n] * B, blocksize)
+    device = rows[0].device if B else torch.device("cuda", torch._C._cuda_getDevice())
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+    if workspace is None:
+        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device)
+    for t, name in ((out, "out"), (workspace, "workspace")):
+        _chk(t, f"flac_encode {name}", torch.uint8)
+        if not t.is_contiguous():
+            raise _lib.SwcError(f"flac_encode: {name} must be contiguous")
+    res = torch.empty(2 * max(B, 1), dtype=torch.int64, device=device)
+    if B == 0:
+        return out, res[:0], res[:0]
+    meta = torch.tensor([r.data_ptr() for r in rows] + lens, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_flac_encode_batch(_ptr(meta[:B]), _ptr(meta[B:]), int(rate), int(blocksize), int(bool(md5)), _ptr(out),
+                                         out.numel(), _ptr(res[:B]), _ptr(res[B:]), _ptr(workspace), workspace.numel(), max_n, B,
+                                         _stream()), "swc_flac_encode_batch")
+    return out, res[:B], res[B:]
+
+
 def stoi_workspace_bytes(B, max_n_in, orig, new):
     """swc_stoi_workspace_bytes of include/swc_metrics.h"""
     v = int(_lib.load().swc_stoi_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))

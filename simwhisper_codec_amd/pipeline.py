@@ -304,6 +304,32 @@ class HostStager:
                 out[i] = b16.as_strided(t.size(), t.stride(), t.storage_offset() - base.storage_offset())
         return out
 
+    def flac_to_host(self, pcm16_tensors, rate, md5=True, blocksize=4096):
+        """pcm16_on_device()'s int16 device tensors -> the utterances' complete .flac file images as host uint8 views of this
+        thread's pinned byte buffer.  ops.flac_encode (swc_flac_encode_batch, include/swc_flac_enc.h) writes the images back to
+        back into one device buffer on the current stream; ONE small read-back brings their sizes, ONE copy the bytes
+        [0, total) — about half of what the PCM16 samples would take.  md5=False leaves the MD5 signature of STREAMINFO zero
+        ("no signature") and skips the one-lane-per-file MD5 kernel.  The producing stream must have been synchronised, or be
+        this one; the views hold until this thread stages its next batch.  An empty waveform has no FLAC file: ValueError."""
+        from . import ops
+        if not pcm16_tensors:
+            return []
+        if any(t.numel() == 0 for t in pcm16_tensors):
+            raise ValueError("flac_to_host: an empty waveform cannot be written as a FLAC file")
+        device = pcm16_tensors[0].device
+        with torch.cuda.device(device):
+            buf, _, sizes = ops.flac_encode([t.reshape(-1) for t in pcm16_tensors], rate, blocksize=blocksize, md5=md5)
+            sizes = [int(v) for v in sizes.cpu()]          # the one small read-back (it waits for the encode)
+            total = sum(sizes)
+            host = self._pinned("bufflac", total)
+            host[:total].copy_(buf[:total], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        out, pos = [], 0
+        for n in sizes:
+            out.append(host[pos:pos + n])
+            pos += n
+        return out
+
     @staticmethod
     def to_host(tensors):
         """device tensors -> host tensors, one copy per source buffer (see _by_buffer) instead of one per utterance.  The copies
