@@ -171,6 +171,17 @@ FLAC_ENC_SIGNATURES = {
     "swc_flac_encode_batch": ([_P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _L, _L, _I, _P], C.c_int),
 }
 
+# include/swc_spectral.h (mel, STFT and log-spectral distances in one call), one to one.  The seventh table of its own
+SPECTRAL_MAX_SCALES = 8                                  # SWC_SPECTRAL_MAX_SCALES
+SPECTRAL_MEL, SPECTRAL_STFT, SPECTRAL_LSD = 1, 2, 4      # SWC_SPECTRAL_MEL / _STFT / _LSD
+SPECTRAL_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
+SPECTRAL_RUN = {w: 32768 // w for w in SPECTRAL_WINDOWS}  # SWC_SPECTRAL_RUN_<W>: frames per workgroup of the frame kernel
+SPECTRAL_SIGNATURES = {
+    "swc_spectral_workspace_bytes": ([_I, _L, C.POINTER(C.c_int32), _I], C.c_int64),
+    "swc_spectral": ([_P, _P, _P, _L, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _P, _L,
+                      _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -192,7 +203,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -11,6 +11,12 @@ The filter that brings the pair to 10 kHz is designed here in float64 (the Kaise
 
 adds ESTOI (Jensen and Taal 2016: STOI's front end, another last step) and SI-SDR (Le Roux et al. 2019: the scale-invariant
 waveform measure, on the samples as given); metrics.estoi and metrics.si_sdr are that call with one metric asked for.
+
+    s = metrics.spectral(ref_list, deg_list, sample_rate=16000)     # {"mel", "stft", "lsd", "parts", "scales"}, one call
+
+gives the magnitude-domain distances (include/swc_spectral.h): multi-scale mel, multi-resolution STFT and log-spectral distance;
+metrics.mel_distance, metrics.stft_distance and metrics.lsd are that call with one metric asked for.  The mel banks are built
+here in float64 (mel_filterbank) and handed to the kernel as a packed f32 table (spectral_table).
 """
 import math
 
@@ -159,3 +165,127 @@ def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
 def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
     """SI-SDR alone, in dB: -> FloatTensor[B] (NaN for an empty pair).  sample_rate is not used by the measure: any rate works."""
     return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",))["si_sdr"]
+
+
+# ---- spectral distances (include/swc_spectral.h) ----
+
+SPECTRAL_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
+SPECTRAL_MELS = (5, 10, 20, 40, 80, 160, 320)
+SPECTRAL_STFT_WINDOWS = (512, 2048)
+SPECTRAL_LSD_WINDOW = 2048
+
+
+def _mel_to_hz(m):
+    """Slaney's scale: linear (200 / 3 Hz per mel) below 1 kHz = 15 mel, logarithmic (a factor 6.4 per 27 mel) above"""
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m < 15.0, m * (200.0 / 3.0), 1000.0 * np.exp((math.log(6.4) / 27.0) * (m - 15.0)))
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f < 1000.0, f / (200.0 / 3.0), 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (math.log(6.4) / 27.0))
+
+
+def mel_filterbank(sample_rate, W, n_mels):
+    """-> float64 [n_mels][W / 2 + 1]: triangles on the bin frequencies f sample_rate / W between n_mels + 2 points equally
+    spaced in mel (Slaney's scale) from 0 to sample_rate / 2, filter m = max(0, min(rising, falling)) scaled by
+    2 / (its upper edge - its lower edge, in Hz)."""
+    sr, W, M = float(sample_rate), int(W), int(n_mels)
+    if sr <= 0 or W < 2 or M < 1:
+        raise SwcError(f"mel_filterbank: sample_rate={sample_rate!r}, W={W!r}, n_mels={n_mels!r}")
+    edges = _mel_to_hz(np.linspace(0.0, float(_hz_to_mel(sr / 2.0)), M + 2))
+    edges[0], edges[-1] = 0.0, sr / 2.0     # the end points are given, not the round trip through the mel scale
+    bins = np.arange(W // 2 + 1, dtype=np.float64) * (sr / W)
+    rising = (bins[None, :] - edges[:M, None]) / (edges[1:M + 1] - edges[:M])[:, None]
+    falling = (edges[2:, None] - bins[None, :]) / (edges[2:] - edges[1:M + 1])[:, None]
+    return np.maximum(0.0, np.minimum(rising, falling)) * (2.0 / (edges[2:] - edges[:M]))[:, None]
+
+
+def pack_filterbanks(banks):
+    """banks = the dense float64 banks of the scales, in scale order -> (first int32 [K], count int32 [K], off int32 [K],
+    w float32 [...]): per filter the first bin with a weight, the number of bins up to its last one (0 for a filter without
+    any: its triangle falls between two bins), where its weights start in w.  Weights are rounded to f32 once, here."""
+    first, count, off, w = [], [], [], []
+    o = 0
+    for fb in banks:
+        for row in np.asarray(fb, dtype=np.float64):
+            nz = np.nonzero(row)[0]
+            if len(nz) == 0:
+                first.append(0); count.append(0); off.append(o)
+                continue
+            a, b = int(nz[0]), int(nz[-1]) + 1
+            first.append(a); count.append(b - a); off.append(o)
+            w.append(row[a:b].astype(np.float32))
+            o += b - a
+    i32 = lambda v: np.asarray(v, dtype=np.int32)
+    return i32(first), i32(count), i32(off), (np.concatenate(w) if w else np.zeros(0, np.float32))
+
+
+_SPECTRAL_TABLES = {}
+
+
+def spectral_table(sample_rate, device):
+    """The fixed scale list (windows 32 .. 2048 with 5 .. 320 mel filters, all flagged MEL; STFT on 512 and 2048; LSD on
+    2048) and its packed mel banks at sample_rate on one device, built once and kept: the `table` of ops.spectral."""
+    device = torch.device(device)
+    key = (int(sample_rate), device.type, device.index)
+    hit = _SPECTRAL_TABLES.get(key)
+    if hit is not None:
+        return hit
+    flags = [_lib.SPECTRAL_MEL | (_lib.SPECTRAL_STFT if w in SPECTRAL_STFT_WINDOWS else 0) | (_lib.SPECTRAL_LSD if w == SPECTRAL_LSD_WINDOW else 0)
+             for w in SPECTRAL_WINDOWS]
+    first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, M) for W, M in zip(SPECTRAL_WINDOWS, SPECTRAL_MELS)])
+    t = {"win": list(SPECTRAL_WINDOWS), "n_mels": list(SPECTRAL_MELS), "flags": flags, "sample_rate": int(sample_rate)}
+    for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
+        t[name] = torch.from_numpy(v).to(device)
+    _SPECTRAL_TABLES[key] = t
+    return t
+
+
+def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS):
+    """Multi-scale mel distance, multi-resolution STFT distance and log-spectral distance of pair i = (ref_list[i] clean,
+    deg_list[i] degraded) in one swc_spectral call: the lists, the cut to the shorter length and the staging of host rows are
+    those of quality().  `want`: which of "mel", "stft", "lsd".  -> dict on `device`: a FloatTensor[B] per wanted metric,
+    "parts" FloatTensor[B][7][4] (mel_s, logmag_s, mag_s, lsd_s of every scale; 0 where the scale does not carry the measure
+    or the measure is not wanted) and "scales" = [(W, n_mels, flags)] as computed.  Every value of an empty pair is NaN.  The
+    rate enters through the mel banks only: any rate works.  Nothing is synchronised."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError("spectral: the metrics are HIP kernels (there is no CPU fallback)")
+    want = tuple(want)
+    if not want or any(w not in ops.SPECTRAL_METRICS for w in want) or len(set(want)) != len(want):
+        raise SwcError(f"spectral: want={want!r}: a non-empty choice of {ops.SPECTRAL_METRICS}")
+    B = len(ref_list)
+    if len(deg_list) != B:
+        raise SwcError(f"spectral: {B} reference and {len(deg_list)} degraded waveforms")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    table = spectral_table(sample_rate, device)
+    mask = sum(ops._SPECTRAL_FLAG[w] for w in want)
+    table = dict(table, flags=[f & mask for f in table["flags"]])     # an unwanted measure costs nothing, and is 0 in parts
+    scales = list(zip(table["win"], table["n_mels"], table["flags"]))
+    if B == 0:
+        res = {w: torch.zeros(0, device=device) for w in want}
+        res["parts"] = torch.zeros((0, len(scales), 4), device=device)
+        res["scales"] = scales
+        return res
+    with torch.cuda.device(device):
+        x_rows, y_rows = _stage(ref_list, deg_list, device)
+        res = ops.spectral(x_rows, y_rows, table, want=want)
+    res["scales"] = scales
+    return res
+
+
+def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+    """the multi-scale mel distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",))["mel"]
+
+
+def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+    """the multi-resolution STFT distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",))["stft"]
+
+
+def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+    """the log-spectral distance (W = 2048) alone: -> FloatTensor[B] (NaN for an empty pair)"""
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",))["lsd"]

@@ -678,6 +678,103 @@ def quality(x_rows, y_rows, table, want=QUALITY_METRICS, max_n_in=None, out=None
     return res
 
 
+SPECTRAL_METRICS = ("mel", "stft", "lsd")
+_SPECTRAL_FLAG = {"mel": _lib.SPECTRAL_MEL, "stft": _lib.SPECTRAL_STFT, "lsd": _lib.SPECTRAL_LSD}
+
+
+def _spectral_windows(win):
+    win = [int(w) for w in win]
+    if len(win) > _lib.SPECTRAL_MAX_SCALES:
+        raise _lib.SwcError(f"spectral: {len(win)} scales (at most {_lib.SPECTRAL_MAX_SCALES})")
+    return win, (C.c_int32 * max(len(win), 1))(*win)
+
+
+def spectral_workspace_bytes(B, max_n_in, win):
+    """swc_spectral_workspace_bytes of include/swc_spectral.h; win = the windows of the scale list"""
+    win, arr = _spectral_windows(win)
+    v = int(_lib.load().swc_spectral_workspace_bytes(int(B), int(max_n_in), arr, len(win)))
+    if v < 0:
+        raise _lib.SwcError(f"spectral: no workspace size for B={B}, max_n_in={max_n_in}, windows {win}")
+    return v
+
+
+def spectral_workspace_layout(B, max_n_in, win):
+    """Where swc_spectral keeps what inside its workspace (csrc/swc_spectral.hip; for tests and debugging, not part of the
+    C-ABI): -> dict(runs = records per row of every scale, rec = the byte offset of every scale's [B][runs][4] f64 records,
+    total).  A scale's run covers SPECTRAL_RUN[W] frames, 8192 samples of the row."""
+    up = lambda v: (v + 255) & ~255
+    L = {"runs": [], "rec": []}
+    o = 0
+    for w in win:
+        T = 1 + max_n_in // (w // 4)
+        runs = -(-T // _lib.SPECTRAL_RUN[w])
+        L["runs"].append(runs)
+        L["rec"].append(o)
+        o += up(B * runs * 32)
+    L["total"] = o
+    return L
+
+
+def spectral(x_rows, y_rows, table, want=SPECTRAL_METRICS, parts=True, max_n_in=None, out=None, workspace=None):
+    """Mel, STFT and log-spectral distance of a ragged batch in one call (include/swc_spectral.h swc_spectral): x_rows / y_rows
+    = lists of 1-D f32 device tensors, pair b of equal length; `table` = the scale list and the packed mel banks
+    (metrics.spectral_table: "win", "n_mels", "flags" host lists, "first", "count", "off" int32 and "w" f32 device tensors);
+    `want` the metrics to compute -> dict of the wanted f32 [B] tensors and, with parts, "parts" f32 [B][n_scales][4]
+    (mel_s, logmag_s, mag_s, lsd_s of every scale; all the work the scales' flags name is then done).  One upload of the
+    row table, one workspace from torch.  max_n_in, out, workspace (tests): the host's length bound, a dict of output tensors
+    to write (mel / stft / lsd / parts, any subset) and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    want = tuple(want)
+    if any(w not in SPECTRAL_METRICS for w in want) or len(set(want)) != len(want) or not (want or parts):
+        raise _lib.SwcError(f"spectral: want={want!r}: a non-empty choice of {SPECTRAL_METRICS}")
+    B = len(x_rows)
+    if B == 0 or len(y_rows) != B:
+        raise _lib.SwcError(f"spectral: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
+    n_in = []
+    for x, y in zip(x_rows, y_rows):
+        _chk(x, "spectral clean row", torch.float32); _chk(y, "spectral degraded row", torch.float32)
+        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
+            raise _lib.SwcError("spectral: a pair is two contiguous 1-D rows of one length")
+        n_in.append(x.numel())
+    device = x_rows[0].device
+    win, c_win = _spectral_windows(table["win"])
+    S = len(win)
+    if len(table["n_mels"]) != S or len(table["flags"]) != S:
+        raise _lib.SwcError("spectral: win, n_mels and flags are lists of one length")
+    c_mels, c_flags = (C.c_int32 * max(S, 1))(*table["n_mels"]), (C.c_int32 * max(S, 1))(*table["flags"])
+    for name in ("first", "count", "off"):
+        _chk(table[name], f"spectral table {name}", torch.int32)
+        if table[name].numel() != sum(table["n_mels"]) or not table[name].is_contiguous():
+            raise _lib.SwcError(f"spectral: table {name} holds one contiguous entry per filter of every scale")
+    _chk(table["w"], "spectral table w", torch.float32)
+    if not table["w"].is_contiguous():
+        raise _lib.SwcError("spectral: the table's weights are contiguous")
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    need = spectral_workspace_bytes(B, max_n, win)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    _chk(workspace, "spectral workspace", torch.uint8)
+    if not workspace.is_contiguous():
+        raise _lib.SwcError("spectral: the workspace is contiguous bytes")
+    out = dict(out or {})
+    res = {}
+    for name in want + (("parts",) if parts else ()):
+        numel = B * S * 4 if name == "parts" else B
+        v = out.get(name)
+        if v is None:
+            v = torch.empty((B, S, 4) if name == "parts" else (B,), device=device, dtype=torch.float32)
+        _chk(v, f"spectral {name}", torch.float32)
+        if v.numel() != numel or not v.is_contiguous():
+            raise _lib.SwcError(f"spectral: {name} is a contiguous tensor of {numel} elements")
+        res[name] = v
+    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_spectral(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, c_win, c_mels, c_flags, S,
+                                _ptr(table["first"]), _ptr(table["count"]), _ptr(table["off"]), _ptr(table["w"]), table["w"].numel(),
+                                _ptr(res.get("mel")), _ptr(res.get("stft")), _ptr(res.get("lsd")), _ptr(res.get("parts")),
+                                _ptr(workspace), workspace.numel(), B, _stream()), "swc_spectral")
+    return res
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""

@@ -1,0 +1,79 @@
+"""Mean multi-scale mel distance, multi-resolution STFT distance and log-spectral distance of a directory of reconstructions
+against the directory of originals, on the GPU (metrics.spectral: one call per batch computes all three):
+
+    python tools/evaluate_spectral.py --original_dir A --synthesized_dir B [--sample_rate 16000] [--batch_size 32] [--verbose]
+
+Files are paired, read and cut as tools/evaluate_stoi.py does it (sorted names, first channel, the shorter length).  Empty
+pairs (the distances are not defined: NaN) are listed by name and left out of the means.
+"""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from evaluate_stoi import load_first_channel, pair_files  # noqa: E402
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    p.add_argument("--original_dir", required=True, help="directory of the original files")
+    p.add_argument("--synthesized_dir", required=True, help="directory of the reconstructed files (same names)")
+    p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (any: it sets the mel banks)")
+    p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_spectral call")
+    p.add_argument("--verbose", action="store_true", help="print every file's values")
+    return p
+
+
+def _mean(values):
+    return sum(values) / len(values) if values else None
+
+
+def summarise(names, mel, stft, lsd):
+    """-> dict: "mel", "stft", "lsd" = the means over the pairs whose value is not NaN (None without one), "empty" = the
+    names left out"""
+    keep = [not (math.isnan(a) or math.isnan(b) or math.isnan(c)) for a, b, c in zip(mel, stft, lsd)]
+    return {"mel": _mean([v for v, k in zip(mel, keep) if k]), "stft": _mean([v for v, k in zip(stft, keep) if k]),
+            "lsd": _mean([v for v, k in zip(lsd, keep) if k]), "empty": [n for n, k in zip(names, keep) if not k]}
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import torch
+    from simwhisper_codec_amd import metrics
+    pairs = pair_files(args.original_dir, args.synthesized_dir)
+    if not pairs:
+        raise SystemExit("no audio files")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    names, cols = [], {"mel": [], "stft": [], "lsd": []}
+    for i in range(0, len(pairs), max(args.batch_size, 1)):
+        chunk = pairs[i:i + max(args.batch_size, 1)]
+        ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
+        deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        q = metrics.spectral(ref, deg, sample_rate=args.sample_rate, device=dev)
+        names += [os.path.basename(o) for o, _ in chunk]
+        for k in cols:
+            cols[k] += [float(v) for v in q[k].cpu()]
+    if args.verbose:
+        for n, a, b, c in zip(names, cols["mel"], cols["stft"], cols["lsd"]):
+            print(f"{n}: " + ("not defined (empty)" if math.isnan(a) else f"mel {a:.4f} STFT {b:.4f} LSD {c:.4f}"))
+    m = summarise(names, cols["mel"], cols["stft"], cols["lsd"])
+    if m["empty"]:
+        print(f"empty, left out of the means ({len(m['empty'])}): " + ", ".join(m["empty"]))
+    scored = len(names) - len(m["empty"])
+    if scored == 0:
+        print("mean mel / STFT / LSD: no pair with samples")
+        return 0
+    print(f"mean mel distance: {m['mel']:.4f} over {scored} pairs")
+    print(f"mean STFT distance: {m['stft']:.4f} over {scored} pairs")
+    print(f"mean LSD: {m['lsd']:.4f} over {scored} pairs")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
