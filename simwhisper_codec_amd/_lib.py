@@ -182,6 +182,17 @@ SPECTRAL_SIGNATURES = {
                       _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_pitch.h (YIN F0 tracks and the pair measures built on them in one call), one to one.  The eighth table of its own
+PITCH_MIN_TAU, PITCH_MAX_TAU = 2, 1024     # SWC_PITCH_MIN_TAU / _MAX_TAU
+PITCH_MIN_WIN, PITCH_MAX_WIN = 16, 2048    # SWC_PITCH_MIN_WIN / _MAX_WIN
+PITCH_MAX_WORK = 1 << 21                   # SWC_PITCH_MAX_WORK: W * tau_max
+PITCH_FRAMES_PER_GROUP = 4                 # SWC_PITCH_FRAMES_PER_GROUP
+PITCH_VALUES, PITCH_COUNTS = 8, 4          # SWC_PITCH_VALUES / _COUNTS
+PITCH_SIGNATURES = {
+    "swc_pitch_workspace_bytes": ([_I, _L, _I, _I, _I], C.c_int64),
+    "swc_pitch": ([_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -203,7 +214,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(PITCH_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -1466,6 +1466,23 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
+    def pitch(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), f_min=62.5, f_max=500.0, tracks=False):
+        """quality() for the pitch measures: encode -> decode -> metrics.pitch of the reconstruction against the input.
+        -> dict on the model's device: "f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1", "voiced_ref", "voiced_deg"
+        (FloatTensor[B] each), "frames" (IntTensor[B]) and, with tracks, "tracks_ref" / "tracks_deg"."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("pitch: the metrics are HIP kernels (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        return metrics.pitch(wav_list, syn, sample_rate=self.input_sample_rate, f_min=f_min, f_max=f_max, device=dev, tracks=tracks)
+
+    @_on_model_device
+    @torch.inference_mode()
     def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
         """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
         11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one

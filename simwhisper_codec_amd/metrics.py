@@ -17,6 +17,12 @@ waveform measure, on the samples as given); metrics.estoi and metrics.si_sdr are
 gives the magnitude-domain distances (include/swc_spectral.h): multi-scale mel, multi-resolution STFT and log-spectral distance;
 metrics.mel_distance, metrics.stft_distance and metrics.lsd are that call with one metric asked for.  The mel banks are built
 here in float64 (mel_filterbank) and handed to the kernel as a packed f32 table (spectral_table).
+
+    p = metrics.pitch(ref_list, deg_list, sample_rate=16000)        # {"f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1", ...}
+    tracks = metrics.f0(wav_list, sample_rate=16000)                # [(f0, voiced)] per waveform
+
+say whether the pitch survived (include/swc_pitch.h): YIN in exact integer arithmetic, a frame every 10 ms, and the measures
+vocoder papers print from the two tracks.
 """
 import math
 
@@ -289,3 +295,66 @@ def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cu
 def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
     """the log-spectral distance (W = 2048) alone: -> FloatTensor[B] (NaN for an empty pair)"""
     return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",))["lsd"]
+
+
+# ---- pitch (include/swc_pitch.h) ----
+
+PITCH_KEYS = ("f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1", "voiced_ref", "voiced_deg")
+
+
+def _tracks(res, side):
+    """the (f0 f32 [T], voiced bool [T]) arrays of every row, cut to the row's own frame count"""
+    f0 = res["f0_" + side]
+    return [(f0[b, :T], f0[b, :T] > 0) for b, T in enumerate(res["frames"])]
+
+
+def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda"), want=PITCH_KEYS, tracks=False):
+    """F0 RMSE in cents, F0 correlation, gross pitch error, voicing decision error and V/UV F1 of pair i = (ref_list[i] clean,
+    deg_list[i] degraded) in one swc_pitch call (YIN in exact integer arithmetic, include/swc_pitch.h): the lists, the cut to the
+    shorter length and the staging of host rows are those of quality().  The call's parameters come from the rate
+    (ops.pitch_params: any rate 8000 .. 48000 with the default f_min, f_max).  `want`: which of PITCH_KEYS.  -> dict on
+    `device`: a FloatTensor[B] per wanted key ("voiced_ref" / "voiced_deg" = the share of voiced frames; NaN where a value's
+    denominator is zero) and "frames" IntTensor[B]; with tracks=True also "tracks_ref" / "tracks_deg": per row (f0 FloatTensor[T],
+    voiced BoolTensor[T]).  Nothing is synchronised."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError("pitch: the metrics are HIP kernels (there is no CPU fallback)")
+    want = tuple(want)
+    if not want or any(w not in PITCH_KEYS for w in want) or len(set(want)) != len(want):
+        raise SwcError(f"pitch: want={want!r}: a non-empty choice of {PITCH_KEYS}")
+    B = len(ref_list)
+    if len(deg_list) != B:
+        raise SwcError(f"pitch: {B} reference and {len(deg_list)} degraded waveforms")
+    params = ops.pitch_params(sample_rate, f_min, f_max)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if B == 0:
+        res = {w: torch.zeros(0, device=device) for w in want}
+        res["frames"] = torch.zeros(0, device=device, dtype=torch.int32)
+        if tracks:
+            res["tracks_ref"], res["tracks_deg"] = [], []
+        return res
+    with torch.cuda.device(device):
+        x_rows, y_rows = _stage(ref_list, deg_list, device)
+        r = ops.pitch(x_rows, y_rows, params, want=("values", "counts") + (("f0_x", "f0_y") if tracks else ()))
+    res = {w: r["values"][:, PITCH_KEYS.index(w)] for w in want}
+    res["frames"] = r["counts"][:, 0]
+    if tracks:
+        res["tracks_ref"], res["tracks_deg"] = _tracks(r, "x"), _tracks(r, "y")
+    return res
+
+
+def f0(wav_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda")):
+    """The F0 track of every waveform of a list (swc_pitch without degraded rows): -> list of (f0 FloatTensor[T] in Hz, 0 where
+    unvoiced, voiced BoolTensor[T]); frame t covers the samples t H .. t H + 3 tau_max with H = round(sample_rate / 100)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError("f0: the tracker is a HIP kernel (there is no CPU fallback)")
+    params = ops.pitch_params(sample_rate, f_min, f_max)
+    if len(wav_list) == 0:
+        return []
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(device):
+        x_rows, _ = _stage(wav_list, wav_list, device)
+        return _tracks(ops.pitch(x_rows, None, params, want=("f0_x",)), "x")

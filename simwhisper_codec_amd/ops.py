@@ -4,6 +4,7 @@ device memory and the stream; every computation is a libswc_hip.so call.
 All activations are frame-major: a reference (B, C, T) tensor lives as [B, T, C].
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -772,6 +773,97 @@ def spectral(x_rows, y_rows, table, want=SPECTRAL_METRICS, parts=True, max_n_in=
                                 _ptr(table["first"]), _ptr(table["count"]), _ptr(table["off"]), _ptr(table["w"]), table["w"].numel(),
                                 _ptr(res.get("mel")), _ptr(res.get("stft")), _ptr(res.get("lsd")), _ptr(res.get("parts")),
                                 _ptr(workspace), workspace.numel(), B, _stream()), "swc_spectral")
+    return res
+
+
+PITCH_OUTPUTS = ("tau_x", "f0_x", "tau_y", "f0_y", "values", "counts")
+
+
+def pitch_params(sample_rate, f_min=62.5, f_max=500.0):
+    """The parameters of a swc_pitch call as derived from the rate: tau_min = floor(sr / f_max), tau_max = ceil(sr / f_min),
+    W = 2 tau_max, H = round(sr / 100) -> dict(sr, W, tau_min, tau_max, H).  16 kHz: 512, 32, 256, 160."""
+    sr = int(sample_rate)
+    if sr < 1 or not (0 < f_min < f_max):
+        raise _lib.SwcError(f"pitch: sample_rate={sample_rate!r}, f_min={f_min!r}, f_max={f_max!r}")
+    tau_min, tau_max = int(math.floor(sr / f_max)), int(math.ceil(sr / f_min))
+    p = dict(sr=sr, W=2 * tau_max, tau_min=tau_min, tau_max=tau_max, H=max(int(round(sr / 100.0)), 1))
+    if not (_lib.PITCH_MIN_TAU <= tau_min < tau_max <= _lib.PITCH_MAX_TAU and _lib.PITCH_MIN_WIN <= p["W"] <= _lib.PITCH_MAX_WIN
+            and p["W"] * tau_max <= _lib.PITCH_MAX_WORK):
+        raise _lib.SwcError(f"pitch: sample_rate={sr}, f_min={f_min}, f_max={f_max} give W={p['W']}, lags {tau_min}..{tau_max}: "
+                            "outside the limits of include/swc_pitch.h")
+    return p
+
+
+def pitch_frames(n, params):
+    """T of a row of n samples: 0 below span = W + tau_max, else 1 + (n - span) // H"""
+    span = params["W"] + params["tau_max"]
+    return 0 if n < span else 1 + (n - span) // params["H"]
+
+
+def pitch_workspace_bytes(B, max_n_in, params):
+    """swc_pitch_workspace_bytes of include/swc_pitch.h"""
+    v = int(_lib.load().swc_pitch_workspace_bytes(int(B), int(max_n_in), int(params["W"]), int(params["tau_max"]), int(params["H"])))
+    if v < 0:
+        raise _lib.SwcError(f"pitch: no workspace size for B={B}, max_n_in={max_n_in}, {params}")
+    return v
+
+
+def pitch(x_rows, y_rows, params, want=PITCH_OUTPUTS, max_n_in=None, ldt=None, out=None, workspace=None):
+    """YIN F0 tracks of a ragged batch and, for pairs, the pitch measures in one call (include/swc_pitch.h swc_pitch): x_rows /
+    y_rows = lists of 1-D f32 device tensors, pair b of equal length; y_rows None tracks x alone (want then holds none of
+    tau_y, f0_y, values).  `params` = pitch_params(rate).  -> dict of the wanted outputs: tau_* int32 [B][ldt], f0_* f32
+    [B][ldt] (entries t >= T of a row are not written: the tensors come from torch.zeros), values f32 [B][8], counts int32
+    [B][4], and "frames" = the host's list of T per row.  max_n_in, ldt, out, workspace (tests): the host's length bound, the
+    track row stride, a dict of output tensors to write and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    want = tuple(want)
+    if not want or any(w not in PITCH_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise _lib.SwcError(f"pitch: want={want!r}: a non-empty choice of {PITCH_OUTPUTS}")
+    if y_rows is None and any(w in ("tau_y", "f0_y", "values") for w in want):
+        raise _lib.SwcError(f"pitch: want={want!r} needs degraded rows")
+    B = len(x_rows)
+    if B == 0 or (y_rows is not None and len(y_rows) != B):
+        raise _lib.SwcError(f"pitch: {B} clean rows and {len(y_rows or [])} degraded rows (equal, non-zero counts expected)")
+    n_in = []
+    for i, x in enumerate(x_rows):
+        _chk(x, "pitch clean row", torch.float32)
+        if x.dim() != 1 or not x.is_contiguous():
+            raise _lib.SwcError("pitch: a row is a contiguous 1-D tensor")
+        if y_rows is not None:
+            y = _chk(y_rows[i], "pitch degraded row", torch.float32)
+            if y.dim() != 1 or y.numel() != x.numel() or not y.is_contiguous():
+                raise _lib.SwcError("pitch: a pair is two contiguous 1-D rows of one length")
+        n_in.append(x.numel())
+    device = x_rows[0].device
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    T = pitch_frames(max_n, params)
+    ldt = T if ldt is None else int(ldt)
+    need = pitch_workspace_bytes(B, max_n, params)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    _chk(workspace, "pitch workspace", torch.uint8)
+    if not workspace.is_contiguous():
+        raise _lib.SwcError("pitch: the workspace is contiguous bytes")
+    out = dict(out or {})
+    res = {}
+    for name in want:
+        dtype = torch.float32 if name in ("f0_x", "f0_y", "values") else torch.int32
+        shape = (B, _lib.PITCH_VALUES) if name == "values" else (B, _lib.PITCH_COUNTS) if name == "counts" else (B, ldt)
+        v = out.get(name)
+        if v is None:
+            v = torch.zeros(shape, device=device, dtype=dtype)
+        _chk(v, f"pitch {name}", dtype)
+        if v.numel() != shape[0] * shape[1] or not v.is_contiguous():
+            raise _lib.SwcError(f"pitch: {name} is a contiguous tensor of {shape[0]} x {shape[1]} elements")
+        res[name] = v
+    rows = [r.data_ptr() for r in x_rows] + ([r.data_ptr() for r in y_rows] if y_rows is not None else [0] * B)
+    meta = torch.tensor(rows + n_in, dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_pitch(_ptr(meta[:B]), _ptr(meta[B:2 * B]) if y_rows is not None else None, _ptr(meta[2 * B:]), max_n,
+                             params["sr"], params["W"], params["tau_min"], params["tau_max"], params["H"],
+                             _ptr(res.get("tau_x")), _ptr(res.get("f0_x")), _ptr(res.get("tau_y")), _ptr(res.get("f0_y")), ldt,
+                             _ptr(res.get("values")), _ptr(res.get("counts")), _ptr(workspace), workspace.numel(), B, _stream()),
+               "swc_pitch")
+    res["frames"] = [pitch_frames(min(n, max_n), params) for n in n_in]
     return res
 
 
