@@ -193,6 +193,19 @@ PITCH_SIGNATURES = {
     "swc_pitch": ([_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_align.h (the lag, overlap, correlation and level ratio of every pair in one call), one to one.  The ninth table of
+# its own
+ALIGN_WAVEFORM, ALIGN_ENVELOPE = 0, 1      # SWC_ALIGN_WAVEFORM / _ENVELOPE
+ALIGN_MAX_LAG = 32768                      # SWC_ALIGN_MAX_LAG
+ALIGN_MAX_N = 1 << 22                      # SWC_ALIGN_MAX_N
+ALIGN_CHUNK, ALIGN_LAG_BLOCK = 4096, 256   # SWC_ALIGN_CHUNK / _LAG_BLOCK
+ALIGN_SPILL = 256                          # SWC_ALIGN_SPILL
+ALIGN_INFO, ALIGN_VALUES = 4, 4            # SWC_ALIGN_INFO / _VALUES
+ALIGN_SIGNATURES = {
+    "swc_align_workspace_bytes": ([_I, _L, _L, _I], C.c_int64),
+    "swc_align": ([_P, _P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -214,7 +227,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(PITCH_SIGNATURES.items()):
+    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(PITCH_SIGNATURES.items()) + list(ALIGN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -23,6 +23,13 @@ here in float64 (mel_filterbank) and handed to the kernel as a packed f32 table 
 
 say whether the pitch survived (include/swc_pitch.h): YIN in exact integer arithmetic, a frame every 10 ms, and the measures
 vocoder papers print from the two tracks.
+
+    a = metrics.align(ref_list, deg_list, sample_rate=16000)        # {"lag", "corr", "gain", "start_ref", "start_deg", "length"}
+    q = metrics.quality(ref_list, deg_list, align="waveform")       # the same call on the aligned views, plus "lag"
+
+find the constant delay of every pair before it is scored (include/swc_align.h): an exact int64 cross-correlation over
++- max_lag_ms, of the waveform or of its rectified envelope.  Every metric above assumes sample-aligned rows; `align=` makes
+them usable on the output of another codec or processing chain.  An aligned pair is two offset views: no audio is copied.
 """
 import math
 
@@ -89,15 +96,19 @@ def stoi_table(sample_rate, device):
     return t
 
 
-def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """STOI of pair i = (ref_list[i] clean, deg_list[i] degraded), two lists of 1-D waveforms at sample_rate (host or device
     tensors); pair i is cut to its shorter length.  -> (d FloatTensor[B], segs IntTensor[B]) on `device`: the score, and the
     number of 30-frame segments it averages.  A pair too short for one segment (fewer than 30 frames of 12.8 ms are left after
     the silent frames are removed) has segs 0 and d 1e-5 (pystoi's convention).  One upload of the row table, one swc_stoi
-    call, one workspace from torch; host rows are staged in one more upload.  Nothing is synchronised."""
+    call, one workspace from torch; host rows are staged in one more upload.  Nothing is synchronised.  align = "waveform" or
+    "envelope": the pairs are aligned first (aligned(): one small read-back) and their views scored; None: the rows as given."""
+    _check_align("stoi", align, max_lag_ms)
     device = torch.device(device)
     if device.type != "cuda":
         raise SwcError("stoi: the metric is a HIP kernel (there is no CPU fallback)")
+    if align is not None:
+        ref_list, deg_list, _ = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
     B = len(ref_list)
     if len(deg_list) != B:
         raise SwcError(f"stoi: {B} reference and {len(deg_list)} degraded waveforms")
@@ -135,15 +146,20 @@ def _stage(ref_list, deg_list, device):
     return rows[0::2], rows[1::2]
 
 
-def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS):
+def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS, align=None, max_lag_ms=50.0):
     """STOI, ESTOI and SI-SDR of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_quality call: the lists, the cut
     to the shorter length and the staging of host rows are those of stoi().  `want`: which of "stoi", "estoi", "si_sdr".
     -> dict on `device`: a FloatTensor[B] per wanted metric and, when stoi or estoi is wanted, "segs" IntTensor[B] (a pair too
     short for one segment has segs 0 and stoi = estoi = 1e-5).  si_sdr is in dB, at sample_rate as given (any rate: it needs
-    no 10 kHz filter), NaN for an empty pair.  Nothing is synchronised."""
+    no 10 kHz filter), NaN for an empty pair.  Nothing is synchronised.  align = "waveform" or "envelope": the pairs are
+    aligned first (aligned(): one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows as given."""
+    _check_align("quality", align, max_lag_ms)
     device = torch.device(device)
     if device.type != "cuda":
         raise SwcError("quality: the metrics are HIP kernels (there is no CPU fallback)")
+    if align is not None:
+        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
+        return dict(quality(xs, ys, sample_rate=sample_rate, device=device, want=want), lag=a["lag"])
     want = tuple(want)
     B = len(ref_list)
     if len(deg_list) != B:
@@ -162,15 +178,15 @@ def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), 
         return ops.quality(x_rows, y_rows, table, want=want)
 
 
-def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """ESTOI alone: -> (d FloatTensor[B], segs IntTensor[B]), the conventions of stoi()"""
-    r = quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("estoi",))
+    r = quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("estoi",), align=align, max_lag_ms=max_lag_ms)
     return r["estoi"], r["segs"]
 
 
-def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """SI-SDR alone, in dB: -> FloatTensor[B] (NaN for an empty pair).  sample_rate is not used by the measure: any rate works."""
-    return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",))["si_sdr"]
+    return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",), align=align, max_lag_ms=max_lag_ms)["si_sdr"]
 
 
 # ---- spectral distances (include/swc_spectral.h) ----
@@ -248,16 +264,22 @@ def spectral_table(sample_rate, device):
     return t
 
 
-def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS):
+def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0):
     """Multi-scale mel distance, multi-resolution STFT distance and log-spectral distance of pair i = (ref_list[i] clean,
     deg_list[i] degraded) in one swc_spectral call: the lists, the cut to the shorter length and the staging of host rows are
     those of quality().  `want`: which of "mel", "stft", "lsd".  -> dict on `device`: a FloatTensor[B] per wanted metric,
     "parts" FloatTensor[B][7][4] (mel_s, logmag_s, mag_s, lsd_s of every scale; 0 where the scale does not carry the measure
     or the measure is not wanted) and "scales" = [(W, n_mels, flags)] as computed.  Every value of an empty pair is NaN.  The
-    rate enters through the mel banks only: any rate works.  Nothing is synchronised."""
+    rate enters through the mel banks only: any rate works.  Nothing is synchronised.  align = "waveform" or "envelope": the
+    pairs are aligned first (aligned(): one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows
+    as given."""
+    _check_align("spectral", align, max_lag_ms)
     device = torch.device(device)
     if device.type != "cuda":
         raise SwcError("spectral: the metrics are HIP kernels (there is no CPU fallback)")
+    if align is not None:
+        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
+        return dict(spectral(xs, ys, sample_rate=sample_rate, device=device, want=want), lag=a["lag"])
     want = tuple(want)
     if not want or any(w not in ops.SPECTRAL_METRICS for w in want) or len(set(want)) != len(want):
         raise SwcError(f"spectral: want={want!r}: a non-empty choice of {ops.SPECTRAL_METRICS}")
@@ -282,19 +304,19 @@ def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"),
     return res
 
 
-def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """the multi-scale mel distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",))["mel"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",), align=align, max_lag_ms=max_lag_ms)["mel"]
 
 
-def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """the multi-resolution STFT distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",))["stft"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",), align=align, max_lag_ms=max_lag_ms)["stft"]
 
 
-def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda")):
+def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
     """the log-spectral distance (W = 2048) alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",))["lsd"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",), align=align, max_lag_ms=max_lag_ms)["lsd"]
 
 
 # ---- pitch (include/swc_pitch.h) ----
@@ -308,17 +330,23 @@ def _tracks(res, side):
     return [(f0[b, :T], f0[b, :T] > 0) for b, T in enumerate(res["frames"])]
 
 
-def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda"), want=PITCH_KEYS, tracks=False):
+def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda"), want=PITCH_KEYS, tracks=False,
+          align=None, max_lag_ms=50.0):
     """F0 RMSE in cents, F0 correlation, gross pitch error, voicing decision error and V/UV F1 of pair i = (ref_list[i] clean,
     deg_list[i] degraded) in one swc_pitch call (YIN in exact integer arithmetic, include/swc_pitch.h): the lists, the cut to the
     shorter length and the staging of host rows are those of quality().  The call's parameters come from the rate
     (ops.pitch_params: any rate 8000 .. 48000 with the default f_min, f_max).  `want`: which of PITCH_KEYS.  -> dict on
     `device`: a FloatTensor[B] per wanted key ("voiced_ref" / "voiced_deg" = the share of voiced frames; NaN where a value's
     denominator is zero) and "frames" IntTensor[B]; with tracks=True also "tracks_ref" / "tracks_deg": per row (f0 FloatTensor[T],
-    voiced BoolTensor[T]).  Nothing is synchronised."""
+    voiced BoolTensor[T]).  Nothing is synchronised.  align = "waveform" or "envelope": the pairs are aligned first (aligned():
+    one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows as given."""
+    _check_align("pitch", align, max_lag_ms)
     device = torch.device(device)
     if device.type != "cuda":
         raise SwcError("pitch: the metrics are HIP kernels (there is no CPU fallback)")
+    if align is not None:
+        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
+        return dict(pitch(xs, ys, sample_rate=sample_rate, f_min=f_min, f_max=f_max, device=device, want=want, tracks=tracks), lag=a["lag"])
     want = tuple(want)
     if not want or any(w not in PITCH_KEYS for w in want) or len(set(want)) != len(want):
         raise SwcError(f"pitch: want={want!r}: a non-empty choice of {PITCH_KEYS}")
@@ -358,3 +386,100 @@ def f0(wav_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device
     with torch.cuda.device(device):
         x_rows, _ = _stage(wav_list, wav_list, device)
         return _tracks(ops.pitch(x_rows, None, params, want=("f0_x",)), "x")
+
+
+# ---- time alignment (include/swc_align.h) ----
+
+ALIGN_KEYS = ("lag", "corr", "gain", "start_ref", "start_deg", "length")
+
+
+def align_range(sample_rate, max_lag_ms):
+    """L of a swc_align call: round(max_lag_ms sample_rate / 1000) samples.  SwcError beyond the limits of include/swc_align.h"""
+    try:
+        ms, sr = float(max_lag_ms), int(sample_rate)
+    except (TypeError, ValueError):
+        raise SwcError(f"align: sample_rate={sample_rate!r}, max_lag_ms={max_lag_ms!r}")
+    if sr < 1 or not (0.0 <= ms < math.inf):
+        raise SwcError(f"align: sample_rate={sample_rate!r}, max_lag_ms={max_lag_ms!r}: a rate >= 1 and a finite range >= 0")
+    L = int(round(ms * sr / 1000.0))
+    if L > _lib.ALIGN_MAX_LAG:
+        raise SwcError(f"align: max_lag_ms={max_lag_ms} at {sr} Hz is {L} samples: at most {_lib.ALIGN_MAX_LAG} (include/swc_align.h)")
+    return L
+
+
+def _check_align(who, align, max_lag_ms):
+    """the align= / max_lag_ms= arguments of the metric calls: None, "waveform" or "envelope"; a finite range >= 0"""
+    if align is None:
+        return
+    if align not in ops.ALIGN_MODES:
+        raise SwcError(f"{who}: align={align!r}: None or one of {tuple(ops.ALIGN_MODES)}")
+    align_range(1, max_lag_ms)
+
+
+def _stage_uncut(ref_list, deg_list, device):
+    """_stage() without the cut: every row at its own length, host rows staged in one upload -> (clean rows, degraded rows)"""
+    rows = [t.reshape(-1) for pair in zip(ref_list, deg_list) for t in pair]
+    host = [i for i, r in enumerate(rows) if r.device.type == "cpu"]
+    if host:
+        staged = torch.cat([rows[i].to(torch.float32) for i in host]).to(device, non_blocking=True)
+        o = 0
+        for i in host:
+            rows[i] = staged[o:o + rows[i].numel()]
+            o += rows[i].numel()
+    rows = [r.to(device=device, dtype=torch.float32).contiguous() for r in rows]
+    return rows[0::2], rows[1::2]
+
+
+def _align_rows(who, ref_list, deg_list, sample_rate, max_lag_ms, mode, device):
+    """the checks and the call shared by align() and aligned() -> (clean rows, degraded rows, result dict)"""
+    if mode not in ops.ALIGN_MODES:
+        raise SwcError(f"{who}: mode={mode!r}: one of {tuple(ops.ALIGN_MODES)}")
+    L = align_range(sample_rate, max_lag_ms)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError(f"{who}: the alignment is a HIP kernel (there is no CPU fallback)")
+    B = len(ref_list)
+    if len(deg_list) != B:
+        raise SwcError(f"{who}: {B} reference and {len(deg_list)} degraded waveforms")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if B == 0:
+        res = {k: torch.zeros(0, device=device, dtype=torch.float32 if k in ("corr", "gain") else torch.int32) for k in ALIGN_KEYS}
+        return [], [], res
+    for r in list(ref_list) + list(deg_list):
+        if r.numel() > _lib.ALIGN_MAX_N:
+            raise SwcError(f"{who}: a row of {r.numel()} samples: at most {_lib.ALIGN_MAX_N} (include/swc_align.h)")
+    with torch.cuda.device(device):
+        x_rows, y_rows = _stage_uncut(ref_list, deg_list, device)
+        r = ops.align(x_rows, y_rows, L, mode, want=("info", "values"))
+    info, values = r["info"], r["values"]
+    res = {"lag": info[:, 0], "corr": values[:, 0], "gain": values[:, 1], "start_ref": info[:, 1], "start_deg": info[:, 2],
+           "length": info[:, 3]}
+    return x_rows, y_rows, res
+
+
+def align(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda")):
+    """The constant delay of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_align call (include/swc_align.h): the
+    integer lag d in -L .. L, L = round(max_lag_ms sample_rate / 1000), that maximises the exact int64 cross-correlation of the
+    two rows (mode "waveform") or of their rectified, mean-free envelopes (mode "envelope": for pairs whose fine structure
+    differs, a vocoder's output for one).  The rows are NOT cut to the shorter length first; host rows are staged in one upload.
+    -> dict on `device`: "lag" IntTensor[B] (> 0: the degraded row is late by that many samples), "corr" FloatTensor[B] (the
+    normalised correlation at that lag over the overlap; NaN for a silent or empty pair), "gain" FloatTensor[B] (the factor
+    that brings the degraded row to the clean row's level over the overlap; reported, not applied), "start_ref", "start_deg",
+    "length" IntTensor[B]: ref[start_ref : start_ref + length] faces deg[start_deg : start_deg + length].  Nothing is
+    synchronised."""
+    return _align_rows("align", ref_list, deg_list, sample_rate, max_lag_ms, mode, device)[2]
+
+
+def aligned(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda")):
+    """align(), then the aligned pairs themselves: -> (ref_views, deg_views, info) with info the dict of align() and the views
+    x[start_ref : start_ref + length], y[start_deg : start_deg + length] of the staged device rows: zero-copy, equal lengths
+    within a pair.  ONE small read-back (the B x 4 int32 of lag, starts and length) synchronises the stream: the views' bounds
+    are host numbers."""
+    x_rows, y_rows, res = _align_rows("aligned", ref_list, deg_list, sample_rate, max_lag_ms, mode, device)
+    if not x_rows:
+        return [], [], res
+    cut = torch.stack([res["start_ref"], res["start_deg"], res["length"]], dim=1).cpu().tolist()
+    xs = [x[x0:x0 + m] for x, (x0, _, m) in zip(x_rows, cut)]
+    ys = [y[y0:y0 + m] for y, (_, y0, m) in zip(y_rows, cut)]
+    return xs, ys, res

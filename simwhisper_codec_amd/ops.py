@@ -867,6 +867,73 @@ def pitch(x_rows, y_rows, params, want=PITCH_OUTPUTS, max_n_in=None, ldt=None, o
     return res
 
 
+ALIGN_OUTPUTS = ("info", "values", "xc")
+ALIGN_MODES = {"waveform": _lib.ALIGN_WAVEFORM, "envelope": _lib.ALIGN_ENVELOPE}
+
+
+def align_workspace_bytes(B, max_nx, max_ny, L):
+    """swc_align_workspace_bytes of include/swc_align.h"""
+    v = int(_lib.load().swc_align_workspace_bytes(int(B), int(max_nx), int(max_ny), int(L)))
+    if v < 0:
+        raise _lib.SwcError(f"align: no workspace size for B={B}, max_nx={max_nx}, max_ny={max_ny}, L={L}")
+    return v
+
+
+def align(x_rows, y_rows, L, mode, want=("info", "values"), max_nx=None, max_ny=None, ldc=None, out=None, workspace=None):
+    """The lag, overlap, correlation and level ratio of every (clean, degraded) pair of a ragged batch in one call
+    (include/swc_align.h swc_align): x_rows / y_rows = lists of 1-D f32 device tensors, the two rows of a pair of any two
+    lengths; L = the search range in samples, mode = "waveform" or "envelope".  -> dict of the wanted outputs: info int32
+    [B][4] = lag, x0, y0, m; values f32 [B][4] = corr, gain, 0, 0; xc int64 [B][ldc], c[d] at column d + L (columns at and
+    beyond 2 L + 1 are not written: the tensor comes from torch.zeros).  max_nx, max_ny, ldc, out, workspace (tests): the
+    host's length bounds, the row stride of xc, a dict of output tensors to write and a 256-byte aligned uint8 workspace to use
+    instead."""
+    lib = _lib.load()
+    want = tuple(want)
+    if any(w not in ALIGN_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise _lib.SwcError(f"align: want={want!r}: a choice of {ALIGN_OUTPUTS}")
+    if mode not in ALIGN_MODES:
+        raise _lib.SwcError(f"align: mode={mode!r}: one of {tuple(ALIGN_MODES)}")
+    L = int(L)
+    if not 0 <= L <= _lib.ALIGN_MAX_LAG:
+        raise _lib.SwcError(f"align: search range L={L} (0..{_lib.ALIGN_MAX_LAG})")
+    B = len(x_rows)
+    if B == 0 or len(y_rows) != B:
+        raise _lib.SwcError(f"align: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
+    for r in list(x_rows) + list(y_rows):
+        _chk(r, "align row", torch.float32)
+        if r.dim() != 1 or not r.is_contiguous():
+            raise _lib.SwcError("align: a row is a contiguous 1-D tensor")
+    n_x, n_y = [r.numel() for r in x_rows], [r.numel() for r in y_rows]
+    device = x_rows[0].device
+    max_nx = max(n_x) if max_nx is None else int(max_nx)
+    max_ny = max(n_y) if max_ny is None else int(max_ny)
+    ldc = 2 * L + 1 if ldc is None else int(ldc)
+    need = align_workspace_bytes(B, max_nx, max_ny, L)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    _chk(workspace, "align workspace", torch.uint8)
+    if not workspace.is_contiguous():
+        raise _lib.SwcError("align: the workspace is contiguous bytes")
+    out = dict(out or {})
+    res = {}
+    for name in want:
+        dtype = {"info": torch.int32, "values": torch.float32, "xc": torch.int64}[name]
+        shape = {"info": (B, _lib.ALIGN_INFO), "values": (B, _lib.ALIGN_VALUES), "xc": (B, ldc)}[name]
+        v = out.get(name)
+        if v is None:
+            v = torch.zeros(shape, device=device, dtype=dtype)
+        _chk(v, f"align {name}", dtype)
+        if v.numel() != shape[0] * shape[1] or not v.is_contiguous():
+            raise _lib.SwcError(f"align: {name} is a contiguous tensor of {shape[0]} x {shape[1]} elements")
+        res[name] = v
+    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_x + n_y,
+                        dtype=torch.int64).to(device, non_blocking=True)
+    _lib.check(lib.swc_align(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:3 * B]), _ptr(meta[3 * B:]), max_nx, max_ny, L,
+                             ALIGN_MODES[mode], _ptr(res.get("info")), _ptr(res.get("values")), _ptr(res.get("xc")), ldc,
+                             _ptr(workspace), workspace.numel(), B, _stream()), "swc_align")
+    return res
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""

@@ -6,6 +6,9 @@ reconstructions against the directory of originals, on the GPU (metrics.pitch: o
 Files are paired, read and cut as tools/evaluate_stoi.py does it (sorted names, first channel, the shorter length).  Every
 measure is averaged over the files where it is defined; a measure that is NaN for a file (no frame, no frame voiced in both,
 ...) leaves that file out of its own mean, and the summary says how many files each mean skipped.
+
+--align {none,waveform,envelope} [--max_lag_ms 50] finds every pair's constant delay first and scores the aligned views; the
+summary then adds the mean and the largest |lag| and the pairs whose correlation is <= 0 or not defined (tools/evaluate_stoi.py).
 """
 import argparse
 import math
@@ -18,7 +21,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
 
 KEYS = ("f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1")
 LABELS = {"f0_rmse_cents": "F0 RMSE (cents)", "f0_corr": "F0 correlation", "gpe": "gross pitch error",
@@ -32,6 +35,7 @@ def build_parser():
     p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (8000 .. 48000)")
     p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_pitch call")
     p.add_argument("--verbose", action="store_true", help="print every file's values")
+    add_align_arguments(p)
     return p
 
 
@@ -63,14 +67,19 @@ def main(argv=None):
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, cols = [], {k: [] for k in KEYS}
+    lags, corrs = [], []
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
         q = metrics.pitch(ref, deg, sample_rate=args.sample_rate, device=dev, want=KEYS)
         names += [os.path.basename(o) for o, _ in chunk]
         for k in KEYS:
             cols[k] += [float(v) for v in q[k].cpu()]
+    if args.align != "none":
+        for line in format_alignment(names, lags, corrs):
+            print(line)
     if args.verbose:
         for j, n in enumerate(names):
             print(f"{n}: " + " ".join(f"{k} {cols[k][j]:.6f}" for k in KEYS))

@@ -6,6 +6,9 @@
 Files are paired, read and cut as tools/evaluate_stoi.py does it (sorted names, first channel, the shorter length).  Pairs too
 short for one STOI segment (segs == 0) are listed by name and left out of the STOI and ESTOI means; empty pairs (SI-SDR is not
 defined: NaN) are left out of the SI-SDR mean.  PESQ is not computed.
+
+--align {none,waveform,envelope} [--max_lag_ms 50] finds every pair's constant delay first and scores the aligned views; the
+summary then adds the mean and the largest |lag| and the pairs whose correlation is <= 0 or not defined (tools/evaluate_stoi.py).
 """
 import argparse
 import math
@@ -18,7 +21,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
 
 
 def build_parser():
@@ -28,6 +31,7 @@ def build_parser():
     p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (8, 10, 16, 24, 32 or 48 kHz)")
     p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_quality call")
     p.add_argument("--verbose", action="store_true", help="print every file's values")
+    add_align_arguments(p)
     return p
 
 
@@ -54,14 +58,19 @@ def main(argv=None):
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, cols = [], {"stoi": [], "estoi": [], "segs": [], "si_sdr": []}
+    lags, corrs = [], []
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
         q = metrics.quality(ref, deg, sample_rate=args.sample_rate, device=dev)
         names += [os.path.basename(o) for o, _ in chunk]
         for k in cols:
             cols[k] += [int(v) if k == "segs" else float(v) for v in q[k].cpu()]
+    if args.align != "none":
+        for line in format_alignment(names, lags, corrs):
+            print(line)
     if args.verbose:
         for n, d, e, s, r in zip(names, cols["stoi"], cols["estoi"], cols["segs"], cols["si_sdr"]):
             left = f"STOI {d:.3f} ESTOI {e:.3f} ({s} segments)" if s else "too short to score"

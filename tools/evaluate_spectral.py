@@ -5,6 +5,9 @@ against the directory of originals, on the GPU (metrics.spectral: one call per b
 
 Files are paired, read and cut as tools/evaluate_stoi.py does it (sorted names, first channel, the shorter length).  Empty
 pairs (the distances are not defined: NaN) are listed by name and left out of the means.
+
+--align {none,waveform,envelope} [--max_lag_ms 50] finds every pair's constant delay first and scores the aligned views; the
+summary then adds the mean and the largest |lag| and the pairs whose correlation is <= 0 or not defined (tools/evaluate_stoi.py).
 """
 import argparse
 import math
@@ -17,7 +20,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
 
 
 def build_parser():
@@ -27,6 +30,7 @@ def build_parser():
     p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (any: it sets the mel banks)")
     p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_spectral call")
     p.add_argument("--verbose", action="store_true", help="print every file's values")
+    add_align_arguments(p)
     return p
 
 
@@ -51,14 +55,19 @@ def main(argv=None):
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, cols = [], {"mel": [], "stft": [], "lsd": []}
+    lags, corrs = [], []
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
         q = metrics.spectral(ref, deg, sample_rate=args.sample_rate, device=dev)
         names += [os.path.basename(o) for o, _ in chunk]
         for k in cols:
             cols[k] += [float(v) for v in q[k].cpu()]
+    if args.align != "none":
+        for line in format_alignment(names, lags, corrs):
+            print(line)
     if args.verbose:
         for n, a, b, c in zip(names, cols["mel"], cols["stft"], cols["lsd"]):
             print(f"{n}: " + ("not defined (empty)" if math.isnan(a) else f"mel {a:.4f} STFT {b:.4f} LSD {c:.4f}"))

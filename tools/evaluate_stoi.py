@@ -5,6 +5,12 @@
 Files are paired by sorted name (.wav / .flac), read through wavio (first channel, clamped to [-1, 1], brought to
 --sample_rate on the host if the file is at another rate), cut to the shorter of the two, and scored in batches.  Pairs too
 short to score (segs == 0) are listed by name and left out of the mean.
+
+    ... --align {none,waveform,envelope} [--max_lag_ms 50]
+
+finds every pair's constant delay first (metrics.aligned, include/swc_align.h) and scores the aligned views: for the output of
+another codec or processing chain.  The summary then adds the mean and the largest |lag| and names the pairs whose correlation
+at the chosen lag is <= 0 or not defined: those were scored, but nothing says they were aligned.
 """
 import argparse
 import os
@@ -22,7 +28,37 @@ def build_parser():
     p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (8, 10, 16, 24, 32 or 48 kHz)")
     p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_stoi call")
     p.add_argument("--verbose", action="store_true", help="print every file's value")
+    add_align_arguments(p)
     return p
+
+
+def add_align_arguments(p):
+    """the two alignment flags shared by the four evaluate tools"""
+    p.add_argument("--align", choices=("none", "waveform", "envelope"), default="none",
+                   help="find every pair's constant delay first and score the aligned views (default: the files as they are)")
+    p.add_argument("--max_lag_ms", type=float, default=50.0, help="search range of --align, in milliseconds either way")
+
+
+def align_pairs(args, ref, deg, dev, lags, corrs):
+    """with --align: the aligned views of a batch (metrics.aligned), its lags and correlations appended to `lags`, `corrs`;
+    without: the batch as it is"""
+    if args.align == "none":
+        return ref, deg
+    from simwhisper_codec_amd import metrics
+    xs, ys, a = metrics.aligned(ref, deg, sample_rate=args.sample_rate, max_lag_ms=args.max_lag_ms, mode=args.align, device=dev)
+    lags += [int(v) for v in a["lag"].cpu()]
+    corrs += [float(v) for v in a["corr"].cpu()]
+    return xs, ys
+
+
+def format_alignment(names, lags, corrs):
+    """the summary lines of an aligned run: mean and largest |lag|, and the pairs whose corr is <= 0 or NaN"""
+    mags = [abs(v) for v in lags]
+    lines = [f"alignment: mean |lag| {sum(mags) / max(len(mags), 1):.3f} samples, largest |lag| {max(mags, default=0)}"]
+    bad = [n for n, c in zip(names, corrs) if not c > 0]
+    if bad:
+        lines.append(f"not aligned (corr <= 0 or not defined) ({len(bad)}): " + ", ".join(bad))
+    return lines
 
 
 def _audio_names(d):
@@ -62,14 +98,19 @@ def main(argv=None):
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
     names, d, segs = [], [], []
+    lags, corrs = [], []
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
+        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
         dv, sv = metrics.stoi(ref, deg, sample_rate=args.sample_rate, device=dev)
         names += [os.path.basename(o) for o, _ in chunk]
         d += [float(v) for v in dv.cpu()]
         segs += [int(v) for v in sv.cpu()]
+    if args.align != "none":
+        for line in format_alignment(names, lags, corrs):
+            print(line)
     if args.verbose:
         for n, v, s in zip(names, d, segs):
             print(f"{n}: STOI {v:.3f} ({s} segments)" if s else f"{n}: too short to score")
