@@ -135,13 +135,17 @@ int swc_gemm(const swc_gemm_args* args, void* stream);
 typedef struct swc_gemm_plan_out {
     int32_t a_dtype;              /* operand mode: SWC_F32 | SWC_BF16 | SWC_F16S | SWC_FP8 */
     int32_t tile_m, tile_n;       /* output rows / columns per tile: 256 | 192 | 128 x 256 (8 waves), 128 | 64 x 128 (4 waves) */
-    int32_t waves;                /* waves per workgroup: 8 or 4 */
+    int32_t waves;                /* waves per workgroup: 8 (2 x 4) or 4 (2 x 2; 1 x 4 when skinny) */
     int32_t plain;                /* 1: plain GEMM staging; 0: implicit-conv staging (taps, stride, pad, K tail, wide row pitch) */
     int32_t act_body;             /* epilogue body compiled in: 0 no activation, 1 GELU, 2 chosen at run time by args->act */
     int32_t k_slice, k_slices;    /* logical elements of K per LDS slice; slices per tap = ceil(K / k_slice) */
     int32_t n_tiles_m, n_tiles_n; /* tiles along M and N */
     int32_t band;                 /* row panels per band of the tile order: 1 (row-major) or 4 */
     int32_t grid, slots;          /* workgroups launched; resident workgroups of the geometry (256 or 512) */
+    int32_t skinny;               /* 1: the "skinny" kernel for convolutions with few rows and a long reduction (bf16 / split-f16;
+                                     plain == 0): 64 x 128 tile, the four waves side by side along N (64 rows x 32 columns each),
+                                     a ring of three LDS stages filled through running per-lane pointers; act_body = 2, band = 1,
+                                     one tile per workgroup (grid = tiles, also beyond `slots`).  0: the other geometries */
 } swc_gemm_plan_out;
 int swc_gemm_plan(const swc_gemm_args* args, swc_gemm_plan_out* plan);
 

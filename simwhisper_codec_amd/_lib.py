@@ -40,7 +40,7 @@ class GemmArgs(C.Structure):
 class GemmPlan(C.Structure):
     """swc_gemm_plan_out of include/swc.h"""
     _fields_ = [(n, C.c_int32) for n in ("a_dtype", "tile_m", "tile_n", "waves", "plain", "act_body", "k_slice", "k_slices",
-                                         "n_tiles_m", "n_tiles_n", "band", "grid", "slots")]
+                                         "n_tiles_m", "n_tiles_n", "band", "grid", "slots", "skinny")]
 
 
 class Dwconv7LnPlan(C.Structure):

@@ -4,6 +4,8 @@
 // One template, two geometries (WAVES_M x WAVES_N waves, each wave 16*MT x 64 outputs):
 //   128 x 128 tile, 4 waves (2x2, MT=4), 64 KiB LDS, 2 workgroups / CU   — f32 and bf16, any shape
 //   256 x 256 tile, 8 waves (2x4, MT=8), 128 KiB LDS, 1 workgroup / CU   — bf16, large M and N
+// A third geometry lives in swc_gemm_skinny.hip (64 x 128 tile, 4 waves side by side along N, staging by running per-lane
+// pointers into a ring of three LDS stages): convolutions with few rows and a long reduction; gemm_plan() below chooses it.
 // K is walked in 128-byte slices (32 f32 / 64 bf16) through a double-buffered LDS image filled by
 // LDS-DMA (glds16 / glds16_s in swc_mfma.h: no VGPR round trip, no ds_write).
 //
@@ -21,6 +23,7 @@
 // CONTIGUOUS output columns 16fh + 4j + e — 64-byte vector stores, full lines per row across fh.
 #include <string.h>
 #include "swc_mfma.h"
+#include "swc_gemm_skinny.h"
 
 // Geometry overrides for A/B measurements exist only in tuning builds (-DSWC_TUNING, tools/build_variant.sh): the
 // shipped library reads no environment variable and keeps no mutable process-wide state.
@@ -776,6 +779,7 @@ struct GemmPlan {
     long slots, grid;  // resident workgroups of the geometry; launched workgroups (grid < tiles: every workgroup walks)
     int nt_mode;       // GemmP::nt_mode
     int stagger;       // GemmP::stagger
+    int skinny;        // 1: the kernel of swc_gemm_skinny.hip (mt, wm, wn then describe its 64 x 128 tile on 1 x 4 waves of 32 columns)
 };
 
 template <int MODE, typename OutT, int MT, int WM, int WN, bool PLAIN, int RB = 128, int ACT = 2>
@@ -885,12 +889,24 @@ int gemm_plan(const swc_gemm_args* a, GemmPlan* g) {
     } else {
         g->mt = ((bf || fs) && half_rows) ? 2 : 4; g->wm = 2; g->wn = 2;
     }
-    const int BM = g->wm * g->mt * 16, BN = g->wn * 64;
     const long es = bf ? 2 : (f8 ? 1 : 4);
     g->bk = (int)(128 / es);
     g->plain = ((a->taps == 1) && (a->K % g->bk == 0) && (a->stride == 1) && (a->pad == 0) && (a->t_in == a->t_out) &&
                 a->lda * es < (1L << 24) && a->ldw * es < (1L << 24))  // 24-bit row pitch: offsets by v_mul_u32_u24
                    ? 1 : 0;
+    // few rows AND a long reduction AND the implicit-conv staging (the samplers' k7 convolutions at the metric batch): the
+    // skinny geometry.  Its staging has no K tail and its lane offsets are 32-bit (operands below 2 GiB).  Plain GEMMs of the same
+    // shapes keep the plain staging of the 64-row tile, which measured 3 - 15 % faster than it (profiles/gemm_skinny_ab.txt).
+    // SWC_SKINNY_MIN_K = 512: launches of taps x K = 576 ... 896 still gain 8 - 21 % (one bf16 shape is unchanged).
+    {
+        const long min_k = tuning_env("SWC_GEMM_SKINNY_K", SWC_SKINNY_MIN_K);
+        const long rows_in = (long)(a->M / a->t_out) * a->t_in;
+        g->skinny = tuning_env("SWC_GEMM_SKINNY", 1) && !big && (bf || fs) && half_rows && !g->plain &&
+                    (long)a->taps * a->K >= min_k && a->K % g->bk == 0 && rows_in * a->lda * es < (1L << 31) &&
+                    (long)a->N * a->ldw * es < (1L << 31);
+    }
+    if (g->skinny) { g->mt = 4; g->wm = 1; g->wn = SWC_SKINNY_WAVES; }
+    const int BM = g->wm * g->mt * 16, BN = g->skinny ? SWC_SKINNY_TILE_N : g->wn * 64;
     // plain GEMMs with 16- / 8-bit outputs: the activation is compiled in (launch)
     g->act_body = (a->c_dtype != SWC_F32 && a->a_dtype != SWC_F32 && g->plain) ? (a->act == SWC_ACT_GELU ? 1 : 0) : 2;
     g->kc_per_tap = (a->K + g->bk - 1) / g->bk;
@@ -898,7 +914,7 @@ int gemm_plan(const swc_gemm_args* a, GemmPlan* g) {
     g->n_tiles_m = (a->M + BM - 1) / BM;
     {
         const int forced = tuning_env("SWC_GEMM_BAND");
-        g->band = forced > 0 ? forced : (g->n_tiles_n >= 12 ? 4 : 1);
+        g->band = g->skinny ? 1 : (forced > 0 ? forced : (g->n_tiles_n >= 12 ? 4 : 1));
     }
     const long nwg = (long)g->n_tiles_n * g->n_tiles_m;
     if (nwg >= (1L << 30)) {
@@ -907,8 +923,8 @@ int gemm_plan(const swc_gemm_args* a, GemmPlan* g) {
     }
     // persistent grid: one workgroup per CU for the 8-wave geometries, two for the 4-wave one (256 CUs)
     const int persist = tuning_env("SWC_GEMM_NOPERSIST") ? 0 : 1;
-    g->slots = 256L * (g->wm * g->wn == 4 ? 2 : 1);
-    g->grid = (persist && nwg > g->slots) ? g->slots : nwg;
+    g->slots = 256L * (g->skinny ? SWC_SKINNY_WG_PER_CU : (g->wm * g->wn == 4 ? 2 : 1));
+    g->grid = (persist && nwg > g->slots && !g->skinny) ? g->slots : nwg;  // the skinny kernel has no tile walk: one tile per workgroup
     // Non-temporal epilogue stores (profiles/r03_gemm_store_policy.txt): alone on the chip the split-f16 fc2 gains 12 % from
     // them (one tile per workgroup, whole 256-byte row pieces behind a long K loop), every other shape loses 0 - 40 %; inside
     // the pipeline the same fc2 / out-proj launches run 1 % SLOWER with them (129 -> 130 us, same-box rocprof A/B): off.
@@ -931,7 +947,7 @@ extern "C" int swc_gemm_plan(const swc_gemm_args* a, swc_gemm_plan_out* out) {
     if (rc != SWC_OK) return rc;
     out->a_dtype = g.mode;
     out->tile_m = g.wm * g.mt * 16;
-    out->tile_n = g.wn * 64;
+    out->tile_n = g.skinny ? SWC_SKINNY_TILE_N : g.wn * 64;
     out->waves = g.wm * g.wn;
     out->plain = g.plain;
     out->act_body = g.act_body;
@@ -942,6 +958,7 @@ extern "C" int swc_gemm_plan(const swc_gemm_args* a, swc_gemm_plan_out* out) {
     out->band = g.band;
     out->grid = (int32_t)g.grid;
     out->slots = (int32_t)g.slots;
+    out->skinny = g.skinny;
     return SWC_OK;
 }
 
@@ -952,6 +969,12 @@ extern "C" int swc_gemm(const swc_gemm_args* a, void* stream) {
     GemmPlan g;
     rc = gemm_plan(a, &g);
     if (rc != SWC_OK) return rc;
+    if (g.skinny) {
+        rc = swc_gemm_skinny_launch(a, g.n_tiles_m, g.n_tiles_n, g.kc_per_tap, swc_sat_counter(), (hipStream_t)stream);
+        if (rc != SWC_OK) return rc;
+        SWC_CHECK_LAUNCH("swc_gemm");
+        return SWC_OK;
+    }
 
     GemmP p;
     p.A = (const char*)a->A;
