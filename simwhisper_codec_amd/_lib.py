@@ -223,14 +223,13 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
-    for name, (argtypes, restype) in PLAIN.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    for name, (argtypes, restype) in list(AUDIO_SIGNATURES.items()) + list(CODES_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) + list(FLAC_SIGNATURES.items()) + list(FLAC_ENC_SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(PITCH_SIGNATURES.items()) + list(ALIGN_SIGNATURES.items()):
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
+    # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
+    for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
+                  FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES):
+        for name, (argtypes, restype) in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = restype
     _lib = lib
     return lib
 

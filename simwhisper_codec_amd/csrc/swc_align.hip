@@ -22,7 +22,7 @@
 //                      integer atomics; then align_values_kernel, one thread per pair: the two float64 values.
 // Everything up to the two final divisions is integer arithmetic: any order gives the same bits.
 // Every store to global memory is an ordinary vector store from plain C++ or an integer atomic.
-#include "swc_common.h"
+#include "swc_metric_common.h"
 #include "swc_align.h"
 
 namespace {
@@ -46,44 +46,8 @@ static_assert(AL_SPILL * 4 * 2 * 128 * 32767LL < (1LL << 31), "a digit's dot pro
 static_assert((long long)SWC_ALIGN_MAX_N * 32767LL * 32767LL < (1LL << 53), "c, Sxx, Exx convert to double exactly");
 static_assert(8 * AL_YB < AL_RAW, "the packed y views read inside the staged span");
 
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ long clamp_len(const int64_t* n, int b, long max_n) {
-    const long v = n[b];
-    return v < 0 ? 0 : (v > max_n ? max_n : v);
-}
-
-__device__ __forceinline__ bool peak_defined(unsigned pk) { return pk < 0x7f800000u; }
-
-__device__ __forceinline__ int peak_exp(unsigned pk) {
-    int e = 0;
-    if (pk != 0u) (void)frexpf(__uint_as_float(pk), &e);  // peak = m 2^e, m in [0.5, 1)
-    return e;
-}
-
-// q of the header: the product is exact, one rounding in rint
-__device__ __forceinline__ int quantise(float v, int e) {
-    double r = rint(ldexp((double)v, 15 - e));
-    r = r > 32767.0 ? 32767.0 : (r < -32767.0 ? -32767.0 : r);
-    return (int)r;
-}
-
 // s of the header from q
 __device__ __forceinline__ int sequence(int q, int mode, int mu) { return mode == SWC_ALIGN_ENVELOPE ? (q < 0 ? -q : q) - mu : q; }
-
-__device__ __forceinline__ unsigned pack16(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
-
-__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c) {
-    return __builtin_amdgcn_sdot2(*reinterpret_cast<const i16x2*>(&a), *reinterpret_cast<const i16x2*>(&b), c, false);
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ void atomic_add_i64(long long* p, long long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);  // two's complement: exact
@@ -408,12 +372,28 @@ bool limits_ok(int B, long max_nx, long max_ny, int L) {
            L <= SWC_ALIGN_MAX_LAG;
 }
 
+// where swc_align keeps what inside its workspace (byte offsets): the peaks [2][B] u32, the sums of |q| [2][B] i64, the
+// accumulators [B][AL_ACC] i64 and c [B][2 L + 1] i64
+struct WsLayout {
+    size_t peaks, sums, acc, c, total;
+};
+
+WsLayout ws_layout(int B, int L) {
+    WsLayout P;
+    size_t o = 0;
+    P.peaks = o; o += up256((size_t)2 * B * sizeof(unsigned));
+    P.sums = o; o += up256((size_t)2 * B * sizeof(long long));
+    P.acc = o; o += up256((size_t)AL_ACC * B * sizeof(long long));
+    P.c = o; o += up256((size_t)B * (size_t)(2L * L + 1) * sizeof(long long));
+    P.total = o;
+    return P;
+}
+
 }  // namespace
 
 extern "C" int64_t swc_align_workspace_bytes(int32_t B, int64_t max_nx, int64_t max_ny, int32_t L) {
     if (!limits_ok(B, max_nx, max_ny, L)) return -1;
-    return (int64_t)(up256((size_t)2 * B * sizeof(unsigned)) + up256((size_t)2 * B * sizeof(long long)) +
-                     up256((size_t)AL_ACC * B * sizeof(long long)) + up256((size_t)B * (size_t)(2L * L + 1) * sizeof(long long)));
+    return (int64_t)ws_layout(B, L).total;
 }
 
 extern "C" int swc_align(const void* const* x_rows, const void* const* y_rows, const int64_t* n_x, const int64_t* n_y,
@@ -427,22 +407,18 @@ extern "C" int swc_align(const void* const* x_rows, const void* const* y_rows, c
     SWC_CHECK_ARG(mode == SWC_ALIGN_WAVEFORM || mode == SWC_ALIGN_ENVELOPE, "swc_align: mode=%d (0 waveform, 1 envelope)", mode);
     const long nl = 2L * L + 1;
     SWC_CHECK_ARG(xc == nullptr || ldc >= nl, "swc_align: ldc=%ld, %ld lags", (long)ldc, nl);
-    const size_t peak_bytes = up256((size_t)2 * B * sizeof(unsigned));
-    const size_t sum_bytes = up256((size_t)2 * B * sizeof(long long));
-    const size_t c_bytes = up256((size_t)B * (size_t)nl * sizeof(long long));
-    const size_t acc_bytes = up256((size_t)AL_ACC * B * sizeof(long long));
-    const size_t total = peak_bytes + sum_bytes + acc_bytes + c_bytes;
-    SWC_CHECK_ARG(workspace_bytes >= (int64_t)total, "swc_align: workspace of %ld bytes, %ld needed (swc_align_workspace_bytes)",
-                  (long)workspace_bytes, (long)total);
+    const WsLayout P = ws_layout(B, L);
+    SWC_CHECK_ARG(workspace_bytes >= (int64_t)P.total, "swc_align: workspace of %ld bytes, %ld needed (swc_align_workspace_bytes)",
+                  (long)workspace_bytes, (long)P.total);
     SWC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "swc_align: workspace must be 256-byte aligned");
     if (B == 0) return SWC_OK;
     hipStream_t st = (hipStream_t)stream;
     unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
-    unsigned* peaks = reinterpret_cast<unsigned*>(base);
-    long long* sums = reinterpret_cast<long long*>(base + peak_bytes);
-    long long* acc = reinterpret_cast<long long*>(base + peak_bytes + sum_bytes);
-    long long* cws = reinterpret_cast<long long*>(base + peak_bytes + sum_bytes + acc_bytes);
-    if (hipMemsetAsync(workspace, 0, total, st) != hipSuccess) {
+    unsigned* peaks = reinterpret_cast<unsigned*>(base + P.peaks);
+    long long* sums = reinterpret_cast<long long*>(base + P.sums);
+    long long* acc = reinterpret_cast<long long*>(base + P.acc);
+    long long* cws = reinterpret_cast<long long*>(base + P.c);
+    if (hipMemsetAsync(workspace, 0, P.total, st) != hipSuccess) {
         (void)hipGetLastError();
         swc_set_error("swc_align: clearing the accumulators failed");
         return SWC_E_LAUNCH;

@@ -20,7 +20,7 @@
 //                        Everything up to d' is integer arithmetic: any order gives the same bits.
 //   pitch_pairs_kernel   one wave per row: counts and float64 sums over the stored f32 tracks in one fixed order.
 // Every store to global memory is an ordinary vector store from plain C++.
-#include "swc_common.h"
+#include "swc_metric_common.h"
 #include "swc_pitch.h"
 
 namespace {
@@ -33,16 +33,7 @@ constexpr int PT_SPILL = 32;       // blocks of four window pairs between two sp
 static_assert(PT_SPILL * 4 * 2 * 128 * 32767LL < (1LL << 31), "a digit's dot products fit int32 between two spills");
 static_assert((long long)SWC_PITCH_MAX_WORK * 65534LL * 65534LL < (1LL << 53), "d tau and S convert to double exactly");
 
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 __host__ __device__ __forceinline__ long frames_of(long n, int span, int H) { return n < span ? 0 : 1 + (n - span) / H; }
-
-__device__ __forceinline__ long row_len(const int64_t* n_in, int b, long max_n) {
-    const long n = n_in[b];
-    return n < 0 ? 0 : (n > max_n ? max_n : n);
-}
 
 // where a wave keeps what inside its LDS region (bytes, every offset a multiple of 16); the host computes the same
 struct Layout {
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(PK_THREADS) void pitch_peak_kernel(const void* cons
                                                                 const int64_t* __restrict__ n_in, long max_n,
                                                                 unsigned* __restrict__ peaks, int B) {
     const int b = blockIdx.y, side = blockIdx.z, tid = threadIdx.x;
-    const long n = row_len(n_in, b, max_n);
+    const long n = clamp_len(n_in, b, max_n);
     const long i0 = (long)blockIdx.x * PK_CHUNK;
     if (i0 >= n) return;  // (an empty row: its address is not read)
     const unsigned* p = reinterpret_cast<const unsigned*>(side == 0 ? x_rows[b] : y_rows[b]);
@@ -88,12 +79,6 @@ __global__ __launch_bounds__(PK_THREADS) void pitch_peak_kernel(const void* cons
         m = v > m ? v : m;
     }
     if ((tid & 63) == 0 && m != 0) atomicMax(peaks + (long)side * B + b, m);
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // exclusive prefix sum over the 64 lanes
@@ -116,12 +101,6 @@ __device__ __forceinline__ int wave_min_i32(int v) {
     return v;
 }
 
-__device__ __forceinline__ unsigned pack16(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
-
-__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c) {
-    return __builtin_amdgcn_sdot2(*reinterpret_cast<const i16x2*>(&a), *reinterpret_cast<const i16x2*>(&b), c, false);
-}
-
 __global__ __launch_bounds__(PT_THREADS) void pitch_frames_kernel(
     const void* const* __restrict__ x_rows, const void* const* __restrict__ y_rows, const int64_t* __restrict__ n_in, long max_n,
     int sr, int W, int tau_min, int tau_max, int H, const unsigned* __restrict__ peaks, int32_t* __restrict__ tau_x,
@@ -130,7 +109,7 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_frames_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int b = blockIdx.y, side = blockIdx.z, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int span = W + tau_max;
-    const long n = row_len(n_in, b, max_n);
+    const long n = clamp_len(n_in, b, max_n);
     const long T = frames_of(n, span, H);
     const long t0 = (long)blockIdx.x * PT_WAVES;
     if (t0 >= T) return;  // uniform over the workgroup (an empty or short row: its address is not read)
@@ -142,7 +121,8 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_frames_kernel(
     if (tau_out != nullptr) tau_out += (long)b * ldt + t;
     if (f0_out != nullptr) f0_out += (long)b * ldt + t;
     const unsigned pk = peaks[(long)side * B + b];
-    if (pk == 0u || pk >= 0x7f800000u) {  // a silent row, or one that is not defined (uniform over the workgroup)
+    // a silent row, or one that is not defined (uniform over the workgroup).  !peak_defined(pk) spelled out: see swc_metric_common.h
+    if (pk == 0u || pk >= 0x7f800000u) {
         if (active && lane == 0) {
             const float f = pk == 0u ? 0.0f : __builtin_nanf("");
             *f0_ws = f;
@@ -151,8 +131,7 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_frames_kernel(
         }
         return;
     }
-    int e;
-    (void)frexpf(__uint_as_float(pk), &e);  // peak = m 2^e, m in [0.5, 1)
+    const int e = peak_exp(pk);
     const Layout L = layout_of(W, tau_max);
     unsigned char* base = lds + (size_t)wave * L.total;
     short* raw = reinterpret_cast<short*>(base + L.raw);
@@ -165,9 +144,7 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_frames_kernel(
     // ---- the frame, quantised ----
     const float* row = reinterpret_cast<const float*>(side == 0 ? x_rows[b] : y_rows[b]) + t * H;  // reads [0, span) of it
     for (int i = lane; i < span; i += 64) {
-        double v = rint(ldexp((double)row[i], 15 - e));
-        v = v > 32767.0 ? 32767.0 : (v < -32767.0 ? -32767.0 : v);
-        raw[i] = (short)(int)v;
+        raw[i] = (short)quantise(row[i], e);
     }
     __syncthreads();
     long long e0 = 0;
@@ -296,10 +273,10 @@ __global__ __launch_bounds__(64) void pitch_pairs_kernel(const int64_t* __restri
     __shared__ double part[64][4];
     __shared__ double tot[4];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const long T = frames_of(row_len(n_in, b, max_n), span, H);
+    const long T = frames_of(clamp_len(n_in, b, max_n), span, H);
     const float* fx = ws_f0 + (long)b * ws_T;
     const float* fy = ws_f0 + ((long)B + b) * ws_T;
-    const bool defined = peaks[b] < 0x7f800000u && (!pair || peaks[(long)B + b] < 0x7f800000u);
+    const bool defined = peak_defined(peaks[b]) && (!pair || peak_defined(peaks[(long)B + b]));
     int n_vx = 0, n_vy = 0, n_vv = 0, n_diff = 0, n_gross = 0;
     double s_c2 = 0.0, s_x = 0.0, s_y = 0.0;
     if (defined) {
@@ -392,13 +369,27 @@ bool params_ok(int W, int tau_max, int H) {
            (long)W * tau_max <= SWC_PITCH_MAX_WORK && H >= 1;
 }
 
+// where swc_pitch keeps what inside its workspace (byte offsets): the peaks [2][B] u32 and the f0 tracks [2][B][T] f32
+struct WsLayout {
+    size_t peaks, f0, total;
+};
+
+WsLayout ws_layout(int B, long T) {
+    WsLayout P;
+    size_t o = 0;
+    P.peaks = o; o += up256((size_t)2 * B * sizeof(unsigned));
+    P.f0 = o; o += up256((size_t)2 * B * (size_t)T * sizeof(float));
+    P.total = o;
+    return P;
+}
+
 }  // namespace
 
 extern "C" int64_t swc_pitch_workspace_bytes(int32_t B, int64_t max_n_in, int32_t W, int32_t tau_max, int32_t H) {
     if (B < 0 || B > 65535 || max_n_in < 0 || !params_ok(W, tau_max, H)) return -1;
     const long T = frames_of(max_n_in, W + tau_max, H);
     if (T >= 0x7fffffffL) return -1;
-    return (int64_t)(up256((size_t)2 * B * sizeof(unsigned)) + up256((size_t)2 * B * (size_t)T * sizeof(float)));
+    return (int64_t)ws_layout(B, T).total;
 }
 
 extern "C" int swc_pitch(const void* const* x_rows, const void* const* y_rows, const int64_t* n_in, int64_t max_n_in, int32_t sr,
@@ -423,16 +414,16 @@ extern "C" int swc_pitch(const void* const* x_rows, const void* const* y_rows, c
     const long T = frames_of(max_n_in, span, H);
     SWC_CHECK_ARG(T < 0x7fffffffL, "swc_pitch: max_n_in=%ld gives 2^31 frames or more", (long)max_n_in);
     SWC_CHECK_ARG(!(tau_x || f0_x || tau_y || f0_y) || ldt >= T, "swc_pitch: ldt=%ld, %ld frames at max_n_in", (long)ldt, T);
-    const size_t peak_bytes = up256((size_t)2 * B * sizeof(unsigned));
-    const size_t total = peak_bytes + up256((size_t)2 * B * (size_t)T * sizeof(float));
-    SWC_CHECK_ARG(workspace_bytes >= (int64_t)total, "swc_pitch: workspace of %ld bytes, %ld needed (swc_pitch_workspace_bytes)",
-                  (long)workspace_bytes, (long)total);
+    const WsLayout P = ws_layout(B, T);
+    SWC_CHECK_ARG(workspace_bytes >= (int64_t)P.total, "swc_pitch: workspace of %ld bytes, %ld needed (swc_pitch_workspace_bytes)",
+                  (long)workspace_bytes, (long)P.total);
     SWC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "swc_pitch: workspace must be 256-byte aligned");
     if (B == 0) return SWC_OK;
     hipStream_t st = (hipStream_t)stream;
     const int sides = y_rows != nullptr ? 2 : 1;
-    unsigned* peaks = reinterpret_cast<unsigned*>(workspace);
-    float* ws_f0 = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + peak_bytes);
+    unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
+    unsigned* peaks = reinterpret_cast<unsigned*>(base + P.peaks);
+    float* ws_f0 = reinterpret_cast<float*>(base + P.f0);
     const long max_n = max_n_in;
     if (hipMemsetAsync(peaks, 0, (size_t)2 * B * sizeof(unsigned), st) != hipSuccess) {
         (void)hipGetLastError();

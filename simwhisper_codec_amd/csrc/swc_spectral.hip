@@ -16,7 +16,7 @@
 // kept in LDS as f32; the FFT stages and the unpacking both read that one table.
 // LDS banking: a butterfly reads two float2 (ds_read_b64, 64 banks); from half-size 32 on a team's lanes read consecutive
 // float2 (conflict-free), the first five stages read with a stride of 2 .. 32 float2 between pairs of lanes (2-way).
-#include "swc_common.h"
+#include "swc_metric_common.h"
 #include "swc_spectral.h"
 
 namespace {
@@ -30,8 +30,6 @@ static_assert(SWC_SPECTRAL_RUN_32 * 32 == SP_RUN_SAMPLES && SWC_SPECTRAL_RUN_64 
                   SWC_SPECTRAL_RUN_2048 * 2048 == SP_RUN_SAMPLES,
               "every run length is 32768 / W");
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool valid_window(int w) { return w >= SWC_SPECTRAL_MIN_WIN && w <= SWC_SPECTRAL_MAX_WIN && (w & (w - 1)) == 0; }
 
 // what the finish kernel needs to know about the scales (passed by value)
@@ -41,11 +39,6 @@ struct Scales {
     long runs[SWC_SPECTRAL_MAX_SCALES];     // records per row
     long rec_off[SWC_SPECTRAL_MAX_SCALES];  // in float64 elements from the workspace's start
 };
-
-__device__ __forceinline__ long row_len(const int64_t* n_in, int b, long max_n) {
-    const long n = n_in[b];
-    return n < 0 ? 0 : (n > max_n ? max_n : n);
-}
 
 __device__ __forceinline__ float clamp_floor(float v) { return v < SP_CLAMP ? SP_CLAMP : v; }  // NaN stays NaN
 
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_frames_kernel(
     __shared__ float s_red[TEAMS][TW][4];
     __shared__ float s_frame[R][4];         // the four sums of every frame of the run
     const int b = blockIdx.y, tid = threadIdx.x, team = tid / TS, lt = tid % TS;
-    const long n = row_len(n_in, b, max_n);
+    const long n = clamp_len(n_in, b, max_n);
     if (n <= 0) return;  // an empty row: its addresses are not read (uniform over the workgroup)
     const long T = 1 + n / H, t0 = (long)blockIdx.x * R;
     if (t0 >= T) return;
@@ -209,7 +202,7 @@ __global__ __launch_bounds__(64) void spectral_finish_kernel(const int64_t* __re
     __shared__ double tile[64][4];
     __shared__ double tot[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const long n = row_len(n_in, b, max_n);
+    const long n = clamp_len(n_in, b, max_n);
     const float nan = __builtin_nanf("");
     double mel_sum = 0.0, stft_sum = 0.0, lsd_val = 0.0;
     for (int s = 0; s < S.n; ++s) {
@@ -273,19 +266,35 @@ void launch_frames(dim3 grid, hipStream_t st, const void* const* x_rows, const v
                        fb_first, fb_count, fb_off, fb_w, fb_w_len, rec, runs);
 }
 
+// where swc_spectral keeps what inside its workspace: per scale the records per row and the byte offset of its
+// [B][runs][4] f64 records.  A scale with a window that is not valid, or with too many frames, has runs -1 and takes no room.
+struct WsLayout {
+    long runs[SWC_SPECTRAL_MAX_SCALES];
+    size_t rec[SWC_SPECTRAL_MAX_SCALES];
+    size_t total;
+    bool ok;  // every scale has a place
+};
+
+WsLayout ws_layout(int B, long max_n, const int32_t* win, int n_scales) {
+    WsLayout P;
+    P.total = 0;
+    P.ok = true;
+    for (int s = 0; s < n_scales; ++s) {
+        P.runs[s] = valid_window(win[s]) ? runs_of(max_n, win[s]) : -1;
+        P.rec[s] = P.total;
+        if (P.runs[s] < 0) P.ok = false;
+        else P.total += up256((size_t)B * (size_t)P.runs[s] * 4 * sizeof(double));
+    }
+    return P;
+}
+
 }  // namespace
 
 extern "C" int64_t swc_spectral_workspace_bytes(int32_t B, int64_t max_n_in, const int32_t* win, int32_t n_scales) {
     if (B < 0 || B > 65535 || max_n_in < 0 || n_scales < 0 || n_scales > SWC_SPECTRAL_MAX_SCALES) return -1;
     if (n_scales > 0 && win == nullptr) return -1;
-    size_t total = 0;
-    for (int s = 0; s < n_scales; ++s) {
-        if (!valid_window(win[s])) return -1;
-        const long runs = runs_of(max_n_in, win[s]);
-        if (runs < 0) return -1;
-        total += up256((size_t)B * (size_t)runs * 4 * sizeof(double));
-    }
-    return (int64_t)total;
+    const WsLayout P = ws_layout(B, max_n_in, win, n_scales);
+    return P.ok ? (int64_t)P.total : -1;
 }
 
 extern "C" int swc_spectral(const void* const* x_rows, const void* const* y_rows, const int64_t* n_in, int64_t max_n_in,
@@ -304,7 +313,7 @@ extern "C" int swc_spectral(const void* const* x_rows, const void* const* y_rows
     int fb_base[SWC_SPECTRAL_MAX_SCALES];
     int n_lsd = 0, filters = 0;
     bool mel_work = false;
-    size_t total = 0;
+    const WsLayout P = ws_layout(B, max_n_in, win, n_scales);
     const int want = (mel ? SWC_SPECTRAL_MEL : 0) | (stft ? SWC_SPECTRAL_STFT : 0) | (lsd ? SWC_SPECTRAL_LSD : 0);
     for (int s = 0; s < n_scales; ++s) {
         const int W = win[s], F = W / 2 + 1;
@@ -315,15 +324,13 @@ extern "C" int swc_spectral(const void* const* x_rows, const void* const* y_rows
         SWC_CHECK_ARG(n_mels[s] >= 0 && n_mels[s] <= F && (!(flags[s] & SWC_SPECTRAL_MEL) || n_mels[s] >= 1),
                       "swc_spectral: scale %d: n_mels=%d (1..%d with W=%d when MEL is flagged)", s, n_mels[s], F, W);
         n_lsd += (flags[s] & SWC_SPECTRAL_LSD) ? 1 : 0;
-        const long runs = runs_of(max_n_in, W);
-        SWC_CHECK_ARG(runs >= 0, "swc_spectral: max_n_in=%ld gives 2^31 frames or more at W=%d", (long)max_n_in, W);
+        SWC_CHECK_ARG(P.runs[s] >= 0, "swc_spectral: max_n_in=%ld gives 2^31 frames or more at W=%d", (long)max_n_in, W);
         S.W[s] = W;
         S.M[s] = n_mels[s];
         S.flags[s] = flags[s];
         S.eff[s] = parts != nullptr ? flags[s] : (flags[s] & want);
-        S.runs[s] = runs;
-        S.rec_off[s] = (long)(total / sizeof(double));
-        total += up256((size_t)B * (size_t)runs * 4 * sizeof(double));
+        S.runs[s] = P.runs[s];
+        S.rec_off[s] = (long)(P.rec[s] / sizeof(double));
         fb_base[s] = filters;
         filters += n_mels[s];
         mel_work = mel_work || (S.eff[s] & SWC_SPECTRAL_MEL);
@@ -331,8 +338,8 @@ extern "C" int swc_spectral(const void* const* x_rows, const void* const* y_rows
     SWC_CHECK_ARG(n_lsd <= 1, "swc_spectral: %d scales are flagged LSD (at most one)", n_lsd);
     SWC_CHECK_ARG(!mel_work || (fb_first && fb_count && fb_off && fb_w), "swc_spectral: null pointer (MEL work needs the mel table)");
     SWC_CHECK_ARG(fb_w_len >= 0 && fb_w_len < 0x7fffffffL, "swc_spectral: fb_w_len=%ld out of range", (long)fb_w_len);
-    SWC_CHECK_ARG(workspace_bytes >= (int64_t)total, "swc_spectral: workspace of %ld bytes, %ld needed (swc_spectral_workspace_bytes)",
-                  (long)workspace_bytes, (long)total);
+    SWC_CHECK_ARG(workspace_bytes >= (int64_t)P.total, "swc_spectral: workspace of %ld bytes, %ld needed (swc_spectral_workspace_bytes)",
+                  (long)workspace_bytes, (long)P.total);
     SWC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "swc_spectral: workspace must be 256-byte aligned");
     if (B == 0) return SWC_OK;
     hipStream_t st = (hipStream_t)stream;

@@ -29,7 +29,7 @@
 //                         order); a fixed tree over the workgroup -> one record per (row, chunk)
 //   sisdr_finish_kernel   one workgroup per row adds the records in ascending chunk order: after pass 1 -> mx, my, alpha,
 //                         after pass 2 -> si_sdr[b]
-#include "swc_common.h"
+#include "swc_metric_common.h"
 #include "swc_audio.h"
 #include "swc_metrics.h"
 #include "swc_quality.h"
@@ -51,8 +51,6 @@ struct Layout {
     long n10max, ld10, Fmax, Mmax;
     size_t x10, y10, e, src, K, Xt, Yt, total;
 };
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 Layout layout(long B, long max_n, int orig, int new_) {
     Layout L;
@@ -106,8 +104,7 @@ __device__ __forceinline__ float window_at(int i) { return (float)(0.5 - 0.5 * c
 
 // the row's length at 10 kHz and its number of frames (n_in clamped into [0, max_n])
 __device__ __forceinline__ long len10(const int64_t* n_in, int b, long max_n, int orig, int new_) {
-    long n = n_in[b];
-    n = n < 0 ? 0 : (n > max_n ? max_n : n);
+    const long n = clamp_len(n_in, b, max_n);
     return orig == new_ ? n : (n * new_ + orig - 1) / orig;
 }
 __device__ __forceinline__ int frames_of(long n10) { return n10 >= ST_FRAME ? (int)((n10 - ST_FRAME) / ST_HOP) + 1 : 0; }
@@ -429,11 +426,6 @@ __global__ __launch_bounds__(256) void estoi_mean_kernel(const int64_t* __restri
     }
 }
 
-__device__ __forceinline__ long sisdr_len(const int64_t* n_in, int b, long max_n) {
-    const long n = n_in[b];
-    return n < 0 ? 0 : (n > max_n ? max_n : n);
-}
-
 // PASS 1: record = sum x, sum y, sum x x, sum x y.  PASS 2: record = sum (alpha x')^2, sum (y' - alpha x')^2, 0, 0.
 // Thread t owns the samples 4 (256 g + t) .. + 3 of the chunk, g = 0 .. SD_GROUPS - 1, and adds them in ascending order
 template <int PASS>
@@ -444,7 +436,7 @@ __global__ __launch_bounds__(SD_THREADS) void sisdr_sums_kernel(const void* cons
                                                                 long chunks) {
     __shared__ double red[SD_THREADS / 64][4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const long n = sisdr_len(n_in, b, max_n), c0 = (long)blockIdx.x * SD_CHUNK;
+    const long n = clamp_len(n_in, b, max_n), c0 = (long)blockIdx.x * SD_CHUNK;
     if (c0 >= n) return;  // (uniform over the workgroup; also every chunk of an empty row, whose addresses are not read)
     const float* x = reinterpret_cast<const float*>(x_rows[b]) + c0;
     const float* y = reinterpret_cast<const float*>(y_rows[b]) + c0;
@@ -520,7 +512,7 @@ __global__ __launch_bounds__(64) void sisdr_finish_kernel(const int64_t* __restr
     __shared__ double tile[64][4];
     __shared__ double tot[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const long n = sisdr_len(n_in, b, max_n);
+    const long n = clamp_len(n_in, b, max_n);
     const long C = (n + SD_CHUNK - 1) / SD_CHUNK;  // <= chunks: the chunks of this row that were written
     const double* r = rec + (long)b * chunks * 4;
     double acc = 0.0;

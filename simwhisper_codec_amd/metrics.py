@@ -75,25 +75,30 @@ def stoi_taps(sample_rate):
     return torch.from_numpy(K.astype(np.float32)), orig, new, width
 
 
+def _cached(cache, sample_rate, device, build):
+    """cache[(rate, device)], from build(device) the first time: a table is built once per rate and device, and kept"""
+    device = torch.device(device)
+    key = (int(sample_rate), device.type, device.index)
+    if key not in cache:
+        cache[key] = build(device)
+    return cache[key]
+
+
 _TABLES = {}
 
 
 def stoi_table(sample_rate, device):
     """The packed table of stoi_taps on one device, built once and kept.  SwcError for a rate whose filter does not fit the
     resampler's LDS tile (44.1 kHz: 441 : 100 with ~320 taps per phase)."""
-    device = torch.device(device)
-    key = (int(sample_rate), device.type, device.index)
-    hit = _TABLES.get(key)
-    if hit is not None:
-        return hit
-    K, orig, new, width = stoi_taps(sample_rate)
-    t = ops.resample_table(sample_rate, FS, device, taps=(K, orig, new, width))
-    floats = (255 // new + 1) * orig + K.shape[1] + min(new, 256) * ((t["run"] | 1) + 1)
-    if floats > RESAMPLE_MAX_LDS_FLOATS:
-        raise SwcError(f"stoi: sample_rate={sample_rate}: the 10 kHz filter ({orig}:{new}, {t['run']} taps per phase) needs {floats} "
-                       f"f32 words of LDS per resampler tile, {RESAMPLE_MAX_LDS_FLOATS} fit; convert to one of {RATES} first")
-    _TABLES[key] = t
-    return t
+    def build(device):
+        K, orig, new, width = stoi_taps(sample_rate)
+        t = ops.resample_table(sample_rate, FS, device, taps=(K, orig, new, width))
+        floats = (255 // new + 1) * orig + K.shape[1] + min(new, 256) * ((t["run"] | 1) + 1)
+        if floats > RESAMPLE_MAX_LDS_FLOATS:
+            raise SwcError(f"stoi: sample_rate={sample_rate}: the 10 kHz filter ({orig}:{new}, {t['run']} taps per phase) needs {floats} "
+                           f"f32 words of LDS per resampler tile, {RESAMPLE_MAX_LDS_FLOATS} fit; convert to one of {RATES} first")
+        return t
+    return _cached(_TABLES, sample_rate, device, build)
 
 
 def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
@@ -103,38 +108,23 @@ def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), ali
     the silent frames are removed) has segs 0 and d 1e-5 (pystoi's convention).  One upload of the row table, one swc_stoi
     call, one workspace from torch; host rows are staged in one more upload.  Nothing is synchronised.  align = "waveform" or
     "envelope": the pairs are aligned first (aligned(): one small read-back) and their views scored; None: the rows as given."""
-    _check_align("stoi", align, max_lag_ms)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError("stoi: the metric is a HIP kernel (there is no CPU fallback)")
-    if align is not None:
-        ref_list, deg_list, _ = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
-    B = len(ref_list)
-    if len(deg_list) != B:
-        raise SwcError(f"stoi: {B} reference and {len(deg_list)} degraded waveforms")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if B == 0:
-        return torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
-    table = stoi_table(sample_rate, device)
-    with torch.cuda.device(device):
-        n = [min(int(x.numel()), int(y.numel())) for x, y in zip(ref_list, deg_list)]
-        rows = [t.reshape(-1)[:k] for pair, k in zip(zip(ref_list, deg_list), n) for t in pair]
-        host = [i for i, r in enumerate(rows) if r.device.type == "cpu"]
-        if host:
-            staged = torch.cat([rows[i].to(torch.float32) for i in host]).to(device, non_blocking=True)
-            o = 0
-            for i in host:
-                rows[i] = staged[o:o + rows[i].numel()]
-                o += rows[i].numel()
-        rows = [r.to(device=device, dtype=torch.float32).contiguous() for r in rows]
-        return ops.stoi(rows[0::2], rows[1::2], table)
+    def score(ref_list, deg_list, device):
+        if len(ref_list) == 0:
+            return torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
+        table = stoi_table(sample_rate, device)
+        with torch.cuda.device(device):
+            return ops.stoi(*_stage(ref_list, deg_list, device), table)
+    return _scored("stoi", "the metric is a HIP kernel", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms)
 
 
-def _stage(ref_list, deg_list, device):
-    """the rows of stoi(): pair i cut to its shorter length, host rows staged in one upload -> (clean rows, degraded rows)"""
-    n = [min(int(x.numel()), int(y.numel())) for x, y in zip(ref_list, deg_list)]
-    rows = [t.reshape(-1)[:k] for pair, k in zip(zip(ref_list, deg_list), n) for t in pair]
+def _stage(ref_list, deg_list, device, cut=True):
+    """The rows of a metric call as contiguous f32 rows on `device`: with cut, pair i cut to its shorter length; every host row
+    in ONE more upload (concatenated, sent non-blocking, sliced back); device rows converted where they stand.
+    -> (clean rows, degraded rows)"""
+    rows = [t.reshape(-1) for pair in zip(ref_list, deg_list) for t in pair]
+    if cut:
+        n = [min(x.numel(), y.numel()) for x, y in zip(rows[0::2], rows[1::2])]
+        rows = [r[:n[i // 2]] for i, r in enumerate(rows)]
     host = [i for i, r in enumerate(rows) if r.device.type == "cpu"]
     if host:
         staged = torch.cat([rows[i].to(torch.float32) for i in host]).to(device, non_blocking=True)
@@ -146,6 +136,38 @@ def _stage(ref_list, deg_list, device):
     return rows[0::2], rows[1::2]
 
 
+def _cuda(who, what, device):
+    """`device` as a torch.device; SwcError unless it is a GPU (`what` names the thing that has no CPU fallback)"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise SwcError(f"{who}: {what} (there is no CPU fallback)")
+    return device
+
+
+def _pairs_on(who, ref_list, deg_list, device):
+    """the pair-count check, then (the first CUDA call of a metric) the device with its index filled in"""
+    if len(deg_list) != len(ref_list):
+        raise SwcError(f"{who}: {len(ref_list)} reference and {len(deg_list)} degraded waveforms")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _scored(who, what, score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=None):
+    """The way into stoi(), quality(), spectral() and pitch().  In this order, and without touching the GPU: the align= /
+    max_lag_ms= check, the device check, `check()` (the call's own arguments), the pair-count check.  Then
+    score(ref_list, deg_list, device with its index) -> the call's result.  With align=, the pairs are aligned first
+    (aligned(): one small read-back), their views scored and, where the result is a dict, "lag" added."""
+    _check_align(who, align, max_lag_ms)
+    device = _cuda(who, what, device)
+    lag = None
+    if align is not None:
+        ref_list, deg_list, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
+        lag = a["lag"]
+    if check is not None:
+        check()
+    res = score(ref_list, deg_list, _pairs_on(who, ref_list, deg_list, device))
+    return dict(res, lag=lag) if lag is not None and isinstance(res, dict) else res
+
+
 def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS, align=None, max_lag_ms=50.0):
     """STOI, ESTOI and SI-SDR of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_quality call: the lists, the cut
     to the shorter length and the staging of host rows are those of stoi().  `want`: which of "stoi", "estoi", "si_sdr".
@@ -153,29 +175,19 @@ def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), 
     short for one segment has segs 0 and stoi = estoi = 1e-5).  si_sdr is in dB, at sample_rate as given (any rate: it needs
     no 10 kHz filter), NaN for an empty pair.  Nothing is synchronised.  align = "waveform" or "envelope": the pairs are
     aligned first (aligned(): one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows as given."""
-    _check_align("quality", align, max_lag_ms)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError("quality: the metrics are HIP kernels (there is no CPU fallback)")
-    if align is not None:
-        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
-        return dict(quality(xs, ys, sample_rate=sample_rate, device=device, want=want), lag=a["lag"])
     want = tuple(want)
-    B = len(ref_list)
-    if len(deg_list) != B:
-        raise SwcError(f"quality: {B} reference and {len(deg_list)} degraded waveforms")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
     front = "stoi" in want or "estoi" in want
-    if B == 0:
-        res = {w: torch.zeros(0, device=device) for w in want}
-        if front:
-            res["segs"] = torch.zeros(0, device=device, dtype=torch.int32)
-        return res
-    table = stoi_table(sample_rate, device) if front else None
-    with torch.cuda.device(device):
-        x_rows, y_rows = _stage(ref_list, deg_list, device)
-        return ops.quality(x_rows, y_rows, table, want=want)
+
+    def score(ref_list, deg_list, device):
+        if len(ref_list) == 0:
+            res = {w: torch.zeros(0, device=device) for w in want}
+            if front:
+                res["segs"] = torch.zeros(0, device=device, dtype=torch.int32)
+            return res
+        table = stoi_table(sample_rate, device) if front else None
+        with torch.cuda.device(device):
+            return ops.quality(*_stage(ref_list, deg_list, device), table, want=want)
+    return _scored("quality", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms)
 
 
 def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
@@ -249,19 +261,15 @@ _SPECTRAL_TABLES = {}
 def spectral_table(sample_rate, device):
     """The fixed scale list (windows 32 .. 2048 with 5 .. 320 mel filters, all flagged MEL; STFT on 512 and 2048; LSD on
     2048) and its packed mel banks at sample_rate on one device, built once and kept: the `table` of ops.spectral."""
-    device = torch.device(device)
-    key = (int(sample_rate), device.type, device.index)
-    hit = _SPECTRAL_TABLES.get(key)
-    if hit is not None:
-        return hit
-    flags = [_lib.SPECTRAL_MEL | (_lib.SPECTRAL_STFT if w in SPECTRAL_STFT_WINDOWS else 0) | (_lib.SPECTRAL_LSD if w == SPECTRAL_LSD_WINDOW else 0)
-             for w in SPECTRAL_WINDOWS]
-    first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, M) for W, M in zip(SPECTRAL_WINDOWS, SPECTRAL_MELS)])
-    t = {"win": list(SPECTRAL_WINDOWS), "n_mels": list(SPECTRAL_MELS), "flags": flags, "sample_rate": int(sample_rate)}
-    for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
-        t[name] = torch.from_numpy(v).to(device)
-    _SPECTRAL_TABLES[key] = t
-    return t
+    def build(device):
+        flags = [_lib.SPECTRAL_MEL | (_lib.SPECTRAL_STFT if w in SPECTRAL_STFT_WINDOWS else 0) | (_lib.SPECTRAL_LSD if w == SPECTRAL_LSD_WINDOW else 0)
+                 for w in SPECTRAL_WINDOWS]
+        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, M) for W, M in zip(SPECTRAL_WINDOWS, SPECTRAL_MELS)])
+        t = {"win": list(SPECTRAL_WINDOWS), "n_mels": list(SPECTRAL_MELS), "flags": flags, "sample_rate": int(sample_rate)}
+        for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
+            t[name] = torch.from_numpy(v).to(device)
+        return t
+    return _cached(_SPECTRAL_TABLES, sample_rate, device, build)
 
 
 def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0):
@@ -273,35 +281,23 @@ def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"),
     rate enters through the mel banks only: any rate works.  Nothing is synchronised.  align = "waveform" or "envelope": the
     pairs are aligned first (aligned(): one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows
     as given."""
-    _check_align("spectral", align, max_lag_ms)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError("spectral: the metrics are HIP kernels (there is no CPU fallback)")
-    if align is not None:
-        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
-        return dict(spectral(xs, ys, sample_rate=sample_rate, device=device, want=want), lag=a["lag"])
     want = tuple(want)
-    if not want or any(w not in ops.SPECTRAL_METRICS for w in want) or len(set(want)) != len(want):
-        raise SwcError(f"spectral: want={want!r}: a non-empty choice of {ops.SPECTRAL_METRICS}")
-    B = len(ref_list)
-    if len(deg_list) != B:
-        raise SwcError(f"spectral: {B} reference and {len(deg_list)} degraded waveforms")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    table = spectral_table(sample_rate, device)
-    mask = sum(ops._SPECTRAL_FLAG[w] for w in want)
-    table = dict(table, flags=[f & mask for f in table["flags"]])     # an unwanted measure costs nothing, and is 0 in parts
-    scales = list(zip(table["win"], table["n_mels"], table["flags"]))
-    if B == 0:
-        res = {w: torch.zeros(0, device=device) for w in want}
-        res["parts"] = torch.zeros((0, len(scales), 4), device=device)
+
+    def score(ref_list, deg_list, device):
+        table = spectral_table(sample_rate, device)
+        mask = sum(ops._SPECTRAL_FLAG[w] for w in want)
+        table = dict(table, flags=[f & mask for f in table["flags"]])     # an unwanted measure costs nothing, and is 0 in parts
+        scales = list(zip(table["win"], table["n_mels"], table["flags"]))
+        if len(ref_list) == 0:
+            res = {w: torch.zeros(0, device=device) for w in want}
+            res["parts"] = torch.zeros((0, len(scales), 4), device=device)
+        else:
+            with torch.cuda.device(device):
+                res = ops.spectral(*_stage(ref_list, deg_list, device), table, want=want)
         res["scales"] = scales
         return res
-    with torch.cuda.device(device):
-        x_rows, y_rows = _stage(ref_list, deg_list, device)
-        res = ops.spectral(x_rows, y_rows, table, want=want)
-    res["scales"] = scales
-    return res
+    return _scored("spectral", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms,
+                   check=lambda: ops._want("spectral", want, ops.SPECTRAL_METRICS))
 
 
 def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
@@ -340,44 +336,33 @@ def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device
     denominator is zero) and "frames" IntTensor[B]; with tracks=True also "tracks_ref" / "tracks_deg": per row (f0 FloatTensor[T],
     voiced BoolTensor[T]).  Nothing is synchronised.  align = "waveform" or "envelope": the pairs are aligned first (aligned():
     one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows as given."""
-    _check_align("pitch", align, max_lag_ms)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError("pitch: the metrics are HIP kernels (there is no CPU fallback)")
-    if align is not None:
-        xs, ys, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
-        return dict(pitch(xs, ys, sample_rate=sample_rate, f_min=f_min, f_max=f_max, device=device, want=want, tracks=tracks), lag=a["lag"])
-    want = tuple(want)
-    if not want or any(w not in PITCH_KEYS for w in want) or len(set(want)) != len(want):
-        raise SwcError(f"pitch: want={want!r}: a non-empty choice of {PITCH_KEYS}")
-    B = len(ref_list)
-    if len(deg_list) != B:
-        raise SwcError(f"pitch: {B} reference and {len(deg_list)} degraded waveforms")
-    params = ops.pitch_params(sample_rate, f_min, f_max)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if B == 0:
-        res = {w: torch.zeros(0, device=device) for w in want}
-        res["frames"] = torch.zeros(0, device=device, dtype=torch.int32)
+    want, params = tuple(want), {}
+
+    def check():
+        ops._want("pitch", want, PITCH_KEYS)
+        params.update(ops.pitch_params(sample_rate, f_min, f_max))
+
+    def score(ref_list, deg_list, device):
+        if len(ref_list) == 0:
+            res = {w: torch.zeros(0, device=device) for w in want}
+            res["frames"] = torch.zeros(0, device=device, dtype=torch.int32)
+            if tracks:
+                res["tracks_ref"], res["tracks_deg"] = [], []
+            return res
+        with torch.cuda.device(device):
+            r = ops.pitch(*_stage(ref_list, deg_list, device), params, want=("values", "counts") + (("f0_x", "f0_y") if tracks else ()))
+        res = {w: r["values"][:, PITCH_KEYS.index(w)] for w in want}
+        res["frames"] = r["counts"][:, 0]
         if tracks:
-            res["tracks_ref"], res["tracks_deg"] = [], []
+            res["tracks_ref"], res["tracks_deg"] = _tracks(r, "x"), _tracks(r, "y")
         return res
-    with torch.cuda.device(device):
-        x_rows, y_rows = _stage(ref_list, deg_list, device)
-        r = ops.pitch(x_rows, y_rows, params, want=("values", "counts") + (("f0_x", "f0_y") if tracks else ()))
-    res = {w: r["values"][:, PITCH_KEYS.index(w)] for w in want}
-    res["frames"] = r["counts"][:, 0]
-    if tracks:
-        res["tracks_ref"], res["tracks_deg"] = _tracks(r, "x"), _tracks(r, "y")
-    return res
+    return _scored("pitch", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=check)
 
 
 def f0(wav_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda")):
     """The F0 track of every waveform of a list (swc_pitch without degraded rows): -> list of (f0 FloatTensor[T] in Hz, 0 where
     unvoiced, voiced BoolTensor[T]); frame t covers the samples t H .. t H + 3 tau_max with H = round(sample_rate / 100)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError("f0: the tracker is a HIP kernel (there is no CPU fallback)")
+    device = _cuda("f0", "the tracker is a HIP kernel", device)
     params = ops.pitch_params(sample_rate, f_min, f_max)
     if len(wav_list) == 0:
         return []
@@ -416,41 +401,20 @@ def _check_align(who, align, max_lag_ms):
     align_range(1, max_lag_ms)
 
 
-def _stage_uncut(ref_list, deg_list, device):
-    """_stage() without the cut: every row at its own length, host rows staged in one upload -> (clean rows, degraded rows)"""
-    rows = [t.reshape(-1) for pair in zip(ref_list, deg_list) for t in pair]
-    host = [i for i, r in enumerate(rows) if r.device.type == "cpu"]
-    if host:
-        staged = torch.cat([rows[i].to(torch.float32) for i in host]).to(device, non_blocking=True)
-        o = 0
-        for i in host:
-            rows[i] = staged[o:o + rows[i].numel()]
-            o += rows[i].numel()
-    rows = [r.to(device=device, dtype=torch.float32).contiguous() for r in rows]
-    return rows[0::2], rows[1::2]
-
-
 def _align_rows(who, ref_list, deg_list, sample_rate, max_lag_ms, mode, device):
     """the checks and the call shared by align() and aligned() -> (clean rows, degraded rows, result dict)"""
     if mode not in ops.ALIGN_MODES:
         raise SwcError(f"{who}: mode={mode!r}: one of {tuple(ops.ALIGN_MODES)}")
     L = align_range(sample_rate, max_lag_ms)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise SwcError(f"{who}: the alignment is a HIP kernel (there is no CPU fallback)")
-    B = len(ref_list)
-    if len(deg_list) != B:
-        raise SwcError(f"{who}: {B} reference and {len(deg_list)} degraded waveforms")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if B == 0:
+    device = _pairs_on(who, ref_list, deg_list, _cuda(who, "the alignment is a HIP kernel", device))
+    if len(ref_list) == 0:
         res = {k: torch.zeros(0, device=device, dtype=torch.float32 if k in ("corr", "gain") else torch.int32) for k in ALIGN_KEYS}
         return [], [], res
     for r in list(ref_list) + list(deg_list):
         if r.numel() > _lib.ALIGN_MAX_N:
             raise SwcError(f"{who}: a row of {r.numel()} samples: at most {_lib.ALIGN_MAX_N} (include/swc_align.h)")
     with torch.cuda.device(device):
-        x_rows, y_rows = _stage_uncut(ref_list, deg_list, device)
+        x_rows, y_rows = _stage(ref_list, deg_list, device, cut=False)
         r = ops.align(x_rows, y_rows, L, mode, want=("info", "values"))
     info, values = r["info"], r["values"]
     res = {"lag": info[:, 0], "corr": values[:, 0], "gain": values[:, 1], "start_ref": info[:, 1], "start_deg": info[:, 2],

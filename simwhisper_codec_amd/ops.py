@@ -48,6 +48,73 @@ def _chk(t, name, dtype=None):
     return t
 
 
+# ---- what the five metric calls (stoi, quality, spectral, pitch, align) share: DESIGN.md "Metric calls: the shared path" ----
+
+def _pair_rows(who, x_rows, y_rows, *, equal_lengths, y_optional=False):
+    """The row checks of a metric call: equal, non-zero counts; every row a contiguous 1-D f32 tensor on the current device;
+    with equal_lengths, the two rows of a pair of one length.  y_optional: y_rows may be None (n_y is then None).
+    -> (n_x, n_y, device)"""
+    B = len(x_rows)
+    alone = y_optional and y_rows is None
+    if B == 0 or (not alone and len(y_rows) != B):
+        raise _lib.SwcError(f"{who}: {B} clean rows and {0 if alone else len(y_rows)} degraded rows (equal, non-zero counts expected)")
+    for side, rows in (("clean", x_rows), ("degraded", () if alone else y_rows)):
+        name = f"{who} {side} row"
+        for r in rows:
+            _chk(r, name, torch.float32)
+            if r.dim() != 1 or not r.is_contiguous():
+                raise _lib.SwcError(f"{who}: a {side} row is a contiguous 1-D tensor")
+    n_x = [r.numel() for r in x_rows]
+    n_y = None if alone else [r.numel() for r in y_rows]
+    if equal_lengths and n_y is not None and n_x != n_y:
+        raise _lib.SwcError(f"{who}: a pair is two contiguous 1-D rows of one length")
+    return n_x, n_y, x_rows[0].device
+
+
+def _row_table(device, *columns):
+    """The row table of a metric call: the columns (row pointers, lengths; B int64 entries each) in ONE host tensor and ONE
+    non-blocking upload: nothing is pinned, kept or synchronised -> the columns' device slices (they keep the table alive)"""
+    B = len(columns[0])
+    meta = torch.tensor(sum(columns, []), dtype=torch.int64).to(device, non_blocking=True)
+    return [meta[i * B:(i + 1) * B] for i in range(len(columns))]
+
+
+def _workspace(who, need, workspace, device):
+    """the call's workspace: `need` bytes from torch (whose allocations are 256-byte aligned, as the C side demands), or the
+    caller's, checked"""
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
+    _chk(workspace, f"{who} workspace", torch.uint8)
+    if not workspace.is_contiguous():
+        raise _lib.SwcError(f"{who}: the workspace is contiguous bytes")
+    return workspace
+
+
+def _outputs(who, specs, out, device, alloc):
+    """The output tensors of a metric call: specs = {name: (shape, dtype)} in order; a tensor of `out` under the same name is
+    checked (dtype, numel, contiguity) and used, the others come from `alloc`: torch.empty where the kernels write every
+    entry, torch.zeros where the docstring promises zeros in the entries they leave alone.  -> {name: tensor}"""
+    out = out or {}
+    res = {}
+    for name, (shape, dtype) in specs.items():
+        v = out.get(name)
+        if v is None:
+            v = alloc(shape, device=device, dtype=dtype)
+        _chk(v, f"{who} {name}", dtype)
+        if v.numel() != math.prod(shape) or not v.is_contiguous():
+            raise _lib.SwcError(f"{who}: {name} is a contiguous tensor of {' x '.join(map(str, shape))} elements")
+        res[name] = v
+    return res
+
+
+def _want(who, want, choices, may_be_empty=False):
+    """`want` as a tuple: distinct names out of `choices`"""
+    want = tuple(want)
+    if any(w not in choices for w in want) or len(set(want)) != len(want) or not (want or may_be_empty):
+        raise _lib.SwcError(f"{who}: want={want!r}: a {'' if may_be_empty else 'non-empty '}choice of {choices}")
+    return want
+
+
 def _gemm_args(A, W, M, N, K, *, out=None, out_dtype=None, lda=None, ldw=None, ldc=None, bias=None, gamma=None,
                residual=None, ldr=None, act=ACT_NONE, taps=1, dil=1, stride=1, pad=0, t_in=None, t_out=None, alpha=1.0,
                out_scale=1.0):
@@ -576,30 +643,16 @@ def stoi(x_rows, y_rows, table, max_n_in=None, d=None, segs=None, workspace=None
     One upload of the row table, one workspace from torch.  max_n_in, d, segs, workspace (tests): the host's length bound,
     the two outputs and a 256-byte aligned uint8 workspace to use instead."""
     lib = _lib.load()
-    B = len(x_rows)
-    if B == 0 or len(y_rows) != B:
-        raise _lib.SwcError(f"stoi: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
-    n_in = []
-    for x, y in zip(x_rows, y_rows):
-        _chk(x, "stoi clean row", torch.float32); _chk(y, "stoi degraded row", torch.float32)
-        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
-            raise _lib.SwcError("stoi: a pair is two contiguous 1-D rows of one length")
-        n_in.append(x.numel())
-    device = x_rows[0].device
+    n_in, _, device = _pair_rows("stoi", x_rows, y_rows, equal_lengths=True)
+    B = len(n_in)
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
-    need = stoi_workspace_bytes(B, max_n, table["orig"], table["new"])
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
-    d = torch.empty(B, device=device, dtype=torch.float32) if d is None else _chk(d, "stoi d", torch.float32)
-    segs = torch.empty(B, device=device, dtype=torch.int32) if segs is None else _chk(segs, "stoi segs", torch.int32)
-    _chk(workspace, "stoi workspace", torch.uint8)
-    if d.numel() != B or segs.numel() != B or not d.is_contiguous() or not segs.is_contiguous() or not workspace.is_contiguous():
-        raise _lib.SwcError("stoi: d and segs are contiguous [B], the workspace contiguous bytes")
-    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
-    _lib.check(lib.swc_stoi(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, table["orig"], table["new"], table["width"],
-                            _ptr(table["taps"]), _ptr(table["start"]), table["run"], _ptr(d), _ptr(segs), _ptr(workspace),
+    workspace = _workspace("stoi", stoi_workspace_bytes(B, max_n, table["orig"], table["new"]), workspace, device)
+    res = _outputs("stoi", {"d": ((B,), torch.float32), "segs": ((B,), torch.int32)}, {"d": d, "segs": segs}, device, torch.empty)
+    xp, yp, n = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_in)
+    _lib.check(lib.swc_stoi(_ptr(xp), _ptr(yp), _ptr(n), max_n, table["orig"], table["new"], table["width"], _ptr(table["taps"]),
+                            _ptr(table["start"]), table["run"], _ptr(res["d"]), _ptr(res["segs"]), _ptr(workspace),
                             workspace.numel(), B, _stream()), "swc_stoi")
-    return d, segs
+    return res["d"], res["segs"]
 
 
 def quality_workspace_bytes(B, max_n_in, orig, new):
@@ -638,44 +691,23 @@ def quality(x_rows, y_rows, table, want=QUALITY_METRICS, max_n_in=None, out=None
     max_n_in, out, workspace (tests): the host's length bound, a dict of output tensors to write (stoi / estoi / si_sdr /
     segs, any subset) and a 256-byte aligned uint8 workspace to use instead."""
     lib = _lib.load()
-    want = tuple(want)
-    if not want or any(w not in QUALITY_METRICS for w in want) or len(set(want)) != len(want):
-        raise _lib.SwcError(f"quality: want={want!r}: a non-empty choice of {QUALITY_METRICS}")
+    want = _want("quality", want, QUALITY_METRICS)
     front = "stoi" in want or "estoi" in want
     if front and table is None:
         raise _lib.SwcError("quality: stoi and estoi need the 10 kHz table (metrics.stoi_table)")
-    B = len(x_rows)
-    if B == 0 or len(y_rows) != B:
-        raise _lib.SwcError(f"quality: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
-    n_in = []
-    for x, y in zip(x_rows, y_rows):
-        _chk(x, "quality clean row", torch.float32); _chk(y, "quality degraded row", torch.float32)
-        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
-            raise _lib.SwcError("quality: a pair is two contiguous 1-D rows of one length")
-        n_in.append(x.numel())
-    device = x_rows[0].device
+    n_in, _, device = _pair_rows("quality", x_rows, y_rows, equal_lengths=True)
+    B = len(n_in)
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
     t = table if front else {"orig": 1, "new": 1, "width": 0, "taps": None, "start": None, "run": 1}
-    need = quality_workspace_bytes(B, max_n, t["orig"], t["new"])
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
-    _chk(workspace, "quality workspace", torch.uint8)
-    out = dict(out or {})
-    res = {}
-    for name in want + (("segs",) if front else ()):
-        dtype = torch.int32 if name == "segs" else torch.float32
-        v = out.get(name)
-        v = torch.empty(B, device=device, dtype=dtype) if v is None else _chk(v, f"quality {name}", dtype)
-        if v.numel() != B or not v.is_contiguous():
-            raise _lib.SwcError(f"quality: {name} is a contiguous [B] tensor")
-        res[name] = v
-    if not workspace.is_contiguous():
-        raise _lib.SwcError("quality: the workspace is contiguous bytes")
-    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
-    _lib.check(lib.swc_quality(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, t["orig"], t["new"], t["width"],
-                               _ptr(t["taps"]), _ptr(t["start"]), t["run"], _ptr(res.get("stoi")), _ptr(res.get("estoi")),
-                               _ptr(res.get("segs")), _ptr(res.get("si_sdr")), _ptr(workspace), workspace.numel(), B, _stream()),
-               "swc_quality")
+    workspace = _workspace("quality", quality_workspace_bytes(B, max_n, t["orig"], t["new"]), workspace, device)
+    specs = {name: ((B,), torch.float32) for name in want}
+    if front:
+        specs["segs"] = ((B,), torch.int32)
+    res = _outputs("quality", specs, out, device, torch.empty)
+    xp, yp, n = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_in)
+    _lib.check(lib.swc_quality(_ptr(xp), _ptr(yp), _ptr(n), max_n, t["orig"], t["new"], t["width"], _ptr(t["taps"]),
+                               _ptr(t["start"]), t["run"], _ptr(res.get("stoi")), _ptr(res.get("estoi")), _ptr(res.get("segs")),
+                               _ptr(res.get("si_sdr")), _ptr(workspace), workspace.numel(), B, _stream()), "swc_quality")
     return res
 
 
@@ -725,19 +757,9 @@ def spectral(x_rows, y_rows, table, want=SPECTRAL_METRICS, parts=True, max_n_in=
     row table, one workspace from torch.  max_n_in, out, workspace (tests): the host's length bound, a dict of output tensors
     to write (mel / stft / lsd / parts, any subset) and a 256-byte aligned uint8 workspace to use instead."""
     lib = _lib.load()
-    want = tuple(want)
-    if any(w not in SPECTRAL_METRICS for w in want) or len(set(want)) != len(want) or not (want or parts):
-        raise _lib.SwcError(f"spectral: want={want!r}: a non-empty choice of {SPECTRAL_METRICS}")
-    B = len(x_rows)
-    if B == 0 or len(y_rows) != B:
-        raise _lib.SwcError(f"spectral: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
-    n_in = []
-    for x, y in zip(x_rows, y_rows):
-        _chk(x, "spectral clean row", torch.float32); _chk(y, "spectral degraded row", torch.float32)
-        if x.dim() != 1 or y.dim() != 1 or x.numel() != y.numel() or not x.is_contiguous() or not y.is_contiguous():
-            raise _lib.SwcError("spectral: a pair is two contiguous 1-D rows of one length")
-        n_in.append(x.numel())
-    device = x_rows[0].device
+    want = _want("spectral", want, SPECTRAL_METRICS, may_be_empty=parts)
+    n_in, _, device = _pair_rows("spectral", x_rows, y_rows, equal_lengths=True)
+    B = len(n_in)
     win, c_win = _spectral_windows(table["win"])
     S = len(win)
     if len(table["n_mels"]) != S or len(table["flags"]) != S:
@@ -751,28 +773,16 @@ def spectral(x_rows, y_rows, table, want=SPECTRAL_METRICS, parts=True, max_n_in=
     if not table["w"].is_contiguous():
         raise _lib.SwcError("spectral: the table's weights are contiguous")
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
-    need = spectral_workspace_bytes(B, max_n, win)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
-    _chk(workspace, "spectral workspace", torch.uint8)
-    if not workspace.is_contiguous():
-        raise _lib.SwcError("spectral: the workspace is contiguous bytes")
-    out = dict(out or {})
-    res = {}
-    for name in want + (("parts",) if parts else ()):
-        numel = B * S * 4 if name == "parts" else B
-        v = out.get(name)
-        if v is None:
-            v = torch.empty((B, S, 4) if name == "parts" else (B,), device=device, dtype=torch.float32)
-        _chk(v, f"spectral {name}", torch.float32)
-        if v.numel() != numel or not v.is_contiguous():
-            raise _lib.SwcError(f"spectral: {name} is a contiguous tensor of {numel} elements")
-        res[name] = v
-    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_in, dtype=torch.int64).to(device, non_blocking=True)
-    _lib.check(lib.swc_spectral(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), max_n, c_win, c_mels, c_flags, S,
-                                _ptr(table["first"]), _ptr(table["count"]), _ptr(table["off"]), _ptr(table["w"]), table["w"].numel(),
-                                _ptr(res.get("mel")), _ptr(res.get("stft")), _ptr(res.get("lsd")), _ptr(res.get("parts")),
-                                _ptr(workspace), workspace.numel(), B, _stream()), "swc_spectral")
+    workspace = _workspace("spectral", spectral_workspace_bytes(B, max_n, win), workspace, device)
+    specs = {name: ((B,), torch.float32) for name in want}
+    if parts:
+        specs["parts"] = ((B, S, 4), torch.float32)
+    res = _outputs("spectral", specs, out, device, torch.empty)
+    xp, yp, n = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_in)
+    _lib.check(lib.swc_spectral(_ptr(xp), _ptr(yp), _ptr(n), max_n, c_win, c_mels, c_flags, S, _ptr(table["first"]),
+                                _ptr(table["count"]), _ptr(table["off"]), _ptr(table["w"]), table["w"].numel(), _ptr(res.get("mel")),
+                                _ptr(res.get("stft")), _ptr(res.get("lsd")), _ptr(res.get("parts")), _ptr(workspace),
+                                workspace.numel(), B, _stream()), "swc_spectral")
     return res
 
 
@@ -816,53 +826,23 @@ def pitch(x_rows, y_rows, params, want=PITCH_OUTPUTS, max_n_in=None, ldt=None, o
     [B][4], and "frames" = the host's list of T per row.  max_n_in, ldt, out, workspace (tests): the host's length bound, the
     track row stride, a dict of output tensors to write and a 256-byte aligned uint8 workspace to use instead."""
     lib = _lib.load()
-    want = tuple(want)
-    if not want or any(w not in PITCH_OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise _lib.SwcError(f"pitch: want={want!r}: a non-empty choice of {PITCH_OUTPUTS}")
+    want = _want("pitch", want, PITCH_OUTPUTS)
     if y_rows is None and any(w in ("tau_y", "f0_y", "values") for w in want):
         raise _lib.SwcError(f"pitch: want={want!r} needs degraded rows")
-    B = len(x_rows)
-    if B == 0 or (y_rows is not None and len(y_rows) != B):
-        raise _lib.SwcError(f"pitch: {B} clean rows and {len(y_rows or [])} degraded rows (equal, non-zero counts expected)")
-    n_in = []
-    for i, x in enumerate(x_rows):
-        _chk(x, "pitch clean row", torch.float32)
-        if x.dim() != 1 or not x.is_contiguous():
-            raise _lib.SwcError("pitch: a row is a contiguous 1-D tensor")
-        if y_rows is not None:
-            y = _chk(y_rows[i], "pitch degraded row", torch.float32)
-            if y.dim() != 1 or y.numel() != x.numel() or not y.is_contiguous():
-                raise _lib.SwcError("pitch: a pair is two contiguous 1-D rows of one length")
-        n_in.append(x.numel())
-    device = x_rows[0].device
+    n_in, _, device = _pair_rows("pitch", x_rows, y_rows, equal_lengths=True, y_optional=True)
+    B = len(n_in)
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
-    T = pitch_frames(max_n, params)
-    ldt = T if ldt is None else int(ldt)
-    need = pitch_workspace_bytes(B, max_n, params)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
-    _chk(workspace, "pitch workspace", torch.uint8)
-    if not workspace.is_contiguous():
-        raise _lib.SwcError("pitch: the workspace is contiguous bytes")
-    out = dict(out or {})
-    res = {}
-    for name in want:
-        dtype = torch.float32 if name in ("f0_x", "f0_y", "values") else torch.int32
-        shape = (B, _lib.PITCH_VALUES) if name == "values" else (B, _lib.PITCH_COUNTS) if name == "counts" else (B, ldt)
-        v = out.get(name)
-        if v is None:
-            v = torch.zeros(shape, device=device, dtype=dtype)
-        _chk(v, f"pitch {name}", dtype)
-        if v.numel() != shape[0] * shape[1] or not v.is_contiguous():
-            raise _lib.SwcError(f"pitch: {name} is a contiguous tensor of {shape[0]} x {shape[1]} elements")
-        res[name] = v
-    rows = [r.data_ptr() for r in x_rows] + ([r.data_ptr() for r in y_rows] if y_rows is not None else [0] * B)
-    meta = torch.tensor(rows + n_in, dtype=torch.int64).to(device, non_blocking=True)
-    _lib.check(lib.swc_pitch(_ptr(meta[:B]), _ptr(meta[B:2 * B]) if y_rows is not None else None, _ptr(meta[2 * B:]), max_n,
-                             params["sr"], params["W"], params["tau_min"], params["tau_max"], params["H"],
-                             _ptr(res.get("tau_x")), _ptr(res.get("f0_x")), _ptr(res.get("tau_y")), _ptr(res.get("f0_y")), ldt,
-                             _ptr(res.get("values")), _ptr(res.get("counts")), _ptr(workspace), workspace.numel(), B, _stream()),
-               "swc_pitch")
+    ldt = pitch_frames(max_n, params) if ldt is None else int(ldt)
+    workspace = _workspace("pitch", pitch_workspace_bytes(B, max_n, params), workspace, device)
+    shapes = {"values": ((B, _lib.PITCH_VALUES), torch.float32), "counts": ((B, _lib.PITCH_COUNTS), torch.int32)}
+    specs = {name: shapes.get(name, ((B, ldt), torch.float32 if name.startswith("f0") else torch.int32)) for name in want}
+    res = _outputs("pitch", specs, out, device, torch.zeros)    # entries t >= T of a track are not written
+    xp, yp, n = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows] if y_rows is not None else [0] * B,
+                           n_in)
+    _lib.check(lib.swc_pitch(_ptr(xp), _ptr(yp) if y_rows is not None else None, _ptr(n), max_n, params["sr"], params["W"],
+                             params["tau_min"], params["tau_max"], params["H"], _ptr(res.get("tau_x")), _ptr(res.get("f0_x")),
+                             _ptr(res.get("tau_y")), _ptr(res.get("f0_y")), ldt, _ptr(res.get("values")), _ptr(res.get("counts")),
+                             _ptr(workspace), workspace.numel(), B, _stream()), "swc_pitch")
     res["frames"] = [pitch_frames(min(n, max_n), params) for n in n_in]
     return res
 
@@ -888,49 +868,24 @@ def align(x_rows, y_rows, L, mode, want=("info", "values"), max_nx=None, max_ny=
     host's length bounds, the row stride of xc, a dict of output tensors to write and a 256-byte aligned uint8 workspace to use
     instead."""
     lib = _lib.load()
-    want = tuple(want)
-    if any(w not in ALIGN_OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise _lib.SwcError(f"align: want={want!r}: a choice of {ALIGN_OUTPUTS}")
+    want = _want("align", want, ALIGN_OUTPUTS, may_be_empty=True)
     if mode not in ALIGN_MODES:
         raise _lib.SwcError(f"align: mode={mode!r}: one of {tuple(ALIGN_MODES)}")
     L = int(L)
     if not 0 <= L <= _lib.ALIGN_MAX_LAG:
         raise _lib.SwcError(f"align: search range L={L} (0..{_lib.ALIGN_MAX_LAG})")
-    B = len(x_rows)
-    if B == 0 or len(y_rows) != B:
-        raise _lib.SwcError(f"align: {B} clean rows and {len(y_rows)} degraded rows (equal, non-zero counts expected)")
-    for r in list(x_rows) + list(y_rows):
-        _chk(r, "align row", torch.float32)
-        if r.dim() != 1 or not r.is_contiguous():
-            raise _lib.SwcError("align: a row is a contiguous 1-D tensor")
-    n_x, n_y = [r.numel() for r in x_rows], [r.numel() for r in y_rows]
-    device = x_rows[0].device
+    n_x, n_y, device = _pair_rows("align", x_rows, y_rows, equal_lengths=False)
+    B = len(n_x)
     max_nx = max(n_x) if max_nx is None else int(max_nx)
     max_ny = max(n_y) if max_ny is None else int(max_ny)
     ldc = 2 * L + 1 if ldc is None else int(ldc)
-    need = align_workspace_bytes(B, max_nx, max_ny, L)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), device=device, dtype=torch.uint8)
-    _chk(workspace, "align workspace", torch.uint8)
-    if not workspace.is_contiguous():
-        raise _lib.SwcError("align: the workspace is contiguous bytes")
-    out = dict(out or {})
-    res = {}
-    for name in want:
-        dtype = {"info": torch.int32, "values": torch.float32, "xc": torch.int64}[name]
-        shape = {"info": (B, _lib.ALIGN_INFO), "values": (B, _lib.ALIGN_VALUES), "xc": (B, ldc)}[name]
-        v = out.get(name)
-        if v is None:
-            v = torch.zeros(shape, device=device, dtype=dtype)
-        _chk(v, f"align {name}", dtype)
-        if v.numel() != shape[0] * shape[1] or not v.is_contiguous():
-            raise _lib.SwcError(f"align: {name} is a contiguous tensor of {shape[0]} x {shape[1]} elements")
-        res[name] = v
-    meta = torch.tensor([r.data_ptr() for r in x_rows] + [r.data_ptr() for r in y_rows] + n_x + n_y,
-                        dtype=torch.int64).to(device, non_blocking=True)
-    _lib.check(lib.swc_align(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:3 * B]), _ptr(meta[3 * B:]), max_nx, max_ny, L,
-                             ALIGN_MODES[mode], _ptr(res.get("info")), _ptr(res.get("values")), _ptr(res.get("xc")), ldc,
-                             _ptr(workspace), workspace.numel(), B, _stream()), "swc_align")
+    workspace = _workspace("align", align_workspace_bytes(B, max_nx, max_ny, L), workspace, device)
+    shapes = {"info": ((B, _lib.ALIGN_INFO), torch.int32), "values": ((B, _lib.ALIGN_VALUES), torch.float32), "xc": ((B, ldc), torch.int64)}
+    res = _outputs("align", {name: shapes[name] for name in want}, out, device, torch.zeros)   # xc beyond 2 L + 1 is not written
+    xp, yp, nx, ny = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_x, n_y)
+    _lib.check(lib.swc_align(_ptr(xp), _ptr(yp), _ptr(nx), _ptr(ny), max_nx, max_ny, L, ALIGN_MODES[mode], _ptr(res.get("info")),
+                             _ptr(res.get("values")), _ptr(res.get("xc")), ldc, _ptr(workspace), workspace.numel(), B, _stream()),
+               "swc_align")
     return res
 
 

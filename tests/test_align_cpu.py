@@ -298,6 +298,30 @@ def test_python_surface_refuses_what_it_cannot_do():
     assert metrics.align_range(44100, 50.0) == 2205
 
 
+def test_stage_with_and_without_the_cut():
+    """metrics._stage on the host: rows of unequal lengths (an empty and a one-sample row against five samples among them), a
+    float64, an int16 and a non-contiguous row -> contiguous f32 rows with the values of the inputs; cut=True is the common
+    prefix of what cut=False gives."""
+    from simwhisper_codec_amd import metrics
+    g = torch.Generator().manual_seed(5)
+    wide = torch.randn(14, generator=g)
+    refs = [torch.randn(7, generator=g, dtype=torch.float64), torch.zeros(0), torch.randn(5, generator=g), wide[::2]]
+    degs = [torch.randn(4, generator=g), torch.randn(5, generator=g), torch.tensor([-3], dtype=torch.int16),
+            torch.tensor([5, -32768, 32767, 0, 1, 2, 3, 4, 9], dtype=torch.int16)]
+    assert not refs[3].is_contiguous()
+    xu, yu = metrics._stage(refs, degs, "cpu", cut=False)
+    xc, yc = metrics._stage(refs, degs, "cpu", cut=True)
+    assert [(x.numel(), y.numel()) for x, y in zip(xu, yu)] == [(7, 4), (0, 5), (5, 1), (7, 9)]
+    assert [(x.numel(), y.numel()) for x, y in zip(xc, yc)] == [(4, 4), (0, 0), (1, 1), (7, 7)]
+    for given, uncut, cut in zip(refs + degs, xu + yu, xc + yc):
+        for r in (uncut, cut):
+            assert r.dtype == torch.float32 and r.dim() == 1 and r.is_contiguous() and r.device.type == "cpu"
+        assert torch.equal(uncut, given.to(torch.float32))
+        assert torch.equal(cut, uncut[:cut.numel()])
+    d = metrics._stage(refs, degs, "cpu")        # the default is the cut
+    assert all(torch.equal(a, b) for a, b in zip(d[0] + d[1], xc + yc))
+
+
 @pytest.mark.parametrize("tool", ["evaluate_stoi", "evaluate_quality", "evaluate_spectral", "evaluate_pitch"])
 def test_tools_parse_the_alignment_flags(tool):
     sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files, score_batches  # noqa: E402, F401
 
 KEYS = ("f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1")
 LABELS = {"f0_rmse_cents": "F0 RMSE (cents)", "f0_corr": "F0 correlation", "gpe": "gross pitch error",
@@ -60,26 +60,12 @@ def format_summary(m, n_files):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    import torch
     from simwhisper_codec_amd import metrics
-    pairs = pair_files(args.original_dir, args.synthesized_dir)
-    if not pairs:
-        raise SystemExit("no audio files")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names, cols = [], {k: [] for k in KEYS}
-    lags, corrs = [], []
-    for i in range(0, len(pairs), max(args.batch_size, 1)):
-        chunk = pairs[i:i + max(args.batch_size, 1)]
-        ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
-        deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
-        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
+
+    def score(ref, deg, dev):
         q = metrics.pitch(ref, deg, sample_rate=args.sample_rate, device=dev, want=KEYS)
-        names += [os.path.basename(o) for o, _ in chunk]
-        for k in KEYS:
-            cols[k] += [float(v) for v in q[k].cpu()]
-    if args.align != "none":
-        for line in format_alignment(names, lags, corrs):
-            print(line)
+        return {k: q[k] for k in KEYS}
+    names, cols, _, _ = score_batches(args, score)
     if args.verbose:
         for j, n in enumerate(names):
             print(f"{n}: " + " ".join(f"{k} {cols[k][j]:.6f}" for k in KEYS))

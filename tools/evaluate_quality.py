@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files, score_batches  # noqa: E402, F401
 
 
 def build_parser():
@@ -51,26 +51,8 @@ def summarise(names, stoi, estoi, segs, si_sdr):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    import torch
     from simwhisper_codec_amd import metrics
-    pairs = pair_files(args.original_dir, args.synthesized_dir)
-    if not pairs:
-        raise SystemExit("no audio files")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names, cols = [], {"stoi": [], "estoi": [], "segs": [], "si_sdr": []}
-    lags, corrs = [], []
-    for i in range(0, len(pairs), max(args.batch_size, 1)):
-        chunk = pairs[i:i + max(args.batch_size, 1)]
-        ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
-        deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
-        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
-        q = metrics.quality(ref, deg, sample_rate=args.sample_rate, device=dev)
-        names += [os.path.basename(o) for o, _ in chunk]
-        for k in cols:
-            cols[k] += [int(v) if k == "segs" else float(v) for v in q[k].cpu()]
-    if args.align != "none":
-        for line in format_alignment(names, lags, corrs):
-            print(line)
+    names, cols, _, _ = score_batches(args, lambda ref, deg, dev: metrics.quality(ref, deg, sample_rate=args.sample_rate, device=dev))
     if args.verbose:
         for n, d, e, s, r in zip(names, cols["stoi"], cols["estoi"], cols["segs"], cols["si_sdr"]):
             left = f"STOI {d:.3f} ESTOI {e:.3f} ({s} segments)" if s else "too short to score"

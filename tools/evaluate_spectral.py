@@ -20,7 +20,7 @@ if ROOT not in sys.path:
 if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files  # noqa: E402
+from evaluate_stoi import add_align_arguments, align_pairs, format_alignment, load_first_channel, pair_files, score_batches  # noqa: E402, F401
 
 
 def build_parser():
@@ -48,26 +48,12 @@ def summarise(names, mel, stft, lsd):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    import torch
     from simwhisper_codec_amd import metrics
-    pairs = pair_files(args.original_dir, args.synthesized_dir)
-    if not pairs:
-        raise SystemExit("no audio files")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    names, cols = [], {"mel": [], "stft": [], "lsd": []}
-    lags, corrs = [], []
-    for i in range(0, len(pairs), max(args.batch_size, 1)):
-        chunk = pairs[i:i + max(args.batch_size, 1)]
-        ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
-        deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
-        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
+
+    def score(ref, deg, dev):
         q = metrics.spectral(ref, deg, sample_rate=args.sample_rate, device=dev)
-        names += [os.path.basename(o) for o, _ in chunk]
-        for k in cols:
-            cols[k] += [float(v) for v in q[k].cpu()]
-    if args.align != "none":
-        for line in format_alignment(names, lags, corrs):
-            print(line)
+        return {k: q[k] for k in ("mel", "stft", "lsd")}
+    names, cols, _, _ = score_batches(args, score)
     if args.verbose:
         for n, a, b, c in zip(names, cols["mel"], cols["stft"], cols["lsd"]):
             print(f"{n}: " + ("not defined (empty)" if math.isnan(a) else f"mel {a:.4f} STFT {b:.4f} LSD {c:.4f}"))

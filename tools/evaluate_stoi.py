@@ -89,28 +89,36 @@ def summarise(names, d, segs):
     return (sum(scored) / len(scored) if scored else None), skipped
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def score_batches(args, score):
+    """The loop of the four evaluate tools: the pairs of the two directories in batches of --batch_size, each batch read,
+    aligned as --align says and handed to score(ref, deg, dev) -> {column: 1-D tensor}; then the alignment summary of an
+    aligned run is printed.  -> (names, {column: the values of every file as Python numbers}, lags, corrs)"""
     import torch
-    from simwhisper_codec_amd import metrics
     pairs = pair_files(args.original_dir, args.synthesized_dir)
     if not pairs:
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
-    names, d, segs = [], [], []
-    lags, corrs = [], []
+    names, cols, lags, corrs = [], {}, [], []
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
         ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
-        dv, sv = metrics.stoi(ref, deg, sample_rate=args.sample_rate, device=dev)
+        for k, v in score(ref, deg, dev).items():
+            cols.setdefault(k, []).extend(v.cpu().tolist())
         names += [os.path.basename(o) for o, _ in chunk]
-        d += [float(v) for v in dv.cpu()]
-        segs += [int(v) for v in sv.cpu()]
     if args.align != "none":
         for line in format_alignment(names, lags, corrs):
             print(line)
+    return names, cols, lags, corrs
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from simwhisper_codec_amd import metrics
+    names, cols, _, _ = score_batches(args, lambda ref, deg, dev: dict(zip(
+        ("d", "segs"), metrics.stoi(ref, deg, sample_rate=args.sample_rate, device=dev))))
+    d, segs = cols["d"], cols["segs"]
     if args.verbose:
         for n, v, s in zip(names, d, segs):
             print(f"{n}: STOI {v:.3f} ({s} segments)" if s else f"{n}: too short to score")
