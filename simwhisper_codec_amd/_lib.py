@@ -206,6 +206,22 @@ ALIGN_SIGNATURES = {
     "swc_align": ([_P, _P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_mcd.h (mel cepstra, and the exact DTW of feature pairs: mel-cepstral distortion), one to one.  The tenth table of
+# its own
+CEPSTRA_MAX_K = 32                         # SWC_CEPSTRA_MAX_K
+DTW_WARP, DTW_DIAGONAL = 0, 1              # SWC_DTW_WARP / _DIAGONAL
+DTW_MAX_FRAMES = 8192                      # SWC_DTW_MAX_FRAMES
+DTW_MAX_D = 32                             # SWC_DTW_MAX_D
+DTW_QBITS = 13                             # SWC_DTW_QBITS
+DTW_STRIP = 256                            # SWC_DTW_STRIP
+DTW_INFO = 4                               # SWC_DTW_INFO
+MCD_SIGNATURES = {
+    "swc_cepstra_workspace_bytes": ([_I, _L, _I, _I], C.c_int64),
+    "swc_cepstra": ([_P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _L, _P, _I, _P, _L, _P, _P, _L, _I, _P], C.c_int),
+    "swc_dtw_workspace_bytes": ([_I, _I, _I, _I], C.c_int64),
+    "swc_dtw": ([_P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _L, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -225,7 +241,7 @@ def load():
         fn.restype = C.c_int
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
-                  FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES):
+                  FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

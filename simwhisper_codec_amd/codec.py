@@ -1483,6 +1483,23 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
+    def mcd(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), dtw=True, band_ms=None, path=False):
+        """quality() for the mel-cepstral distortion: encode -> decode -> metrics.mcd of the reconstruction against the input.
+        -> dict on the model's device: "mcd" (FloatTensor[B], dB), "frames_ref", "frames_deg", "steps" (IntTensor[B]) and,
+        with path, "path"."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("mcd: the metrics are HIP kernels (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        return metrics.mcd(wav_list, syn, sample_rate=self.input_sample_rate, dtw=dtw, band_ms=band_ms, path=path, device=dev)
+
+    @_on_model_device
+    @torch.inference_mode()
     def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
         """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
         11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one

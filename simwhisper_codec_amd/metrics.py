@@ -447,3 +447,137 @@ def aligned(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="wavefo
     xs = [x[x0:x0 + m] for x, (x0, _, m) in zip(x_rows, cut)]
     ys = [y[y0:y0 + m] for y, (_, y0, m) in zip(y_rows, cut)]
     return xs, ys, res
+
+
+# ---- mel-cepstral distortion (include/swc_mcd.h) ----
+
+MCD_MELS = 80
+MCD_COEFFS = 13                                          # c1 .. c13: c0 (the level) is left out
+MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)          # mean cepstral distance -> dB
+MAX_FRAMES = _lib.DTW_MAX_FRAMES
+
+
+def mcd_params(sample_rate):
+    """-> (W, H): the smallest power of two >= 25 ms of samples, and 10 ms of samples (rounded)"""
+    sr = int(sample_rate)
+    if sr < 1:
+        raise SwcError(f"mcd: sample_rate={sample_rate!r}")
+    W = 1 << max(int(math.ceil(0.025 * sr)) - 1, 0).bit_length()
+    H = max(int(round(0.010 * sr)), 1)
+    if W not in ops.CEPSTRA_WINDOWS or H > W:
+        raise SwcError(f"mcd: sample_rate={sr} gives a window of {W} samples and a hop of {H}: windows of {ops.CEPSTRA_WINDOWS} "
+                       "(include/swc_mcd.h)")
+    return W, H
+
+
+def dct_matrix(n_coeffs, n_mels, first=1):
+    """-> float64 [n_coeffs][n_mels]: rows first .. first + n_coeffs - 1 of the orthonormal DCT-II,
+    sqrt(2 / M) cos(pi k (m + 1/2) / M), row 0 scaled by sqrt(1 / 2) more"""
+    k = np.arange(first, first + n_coeffs, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    d = math.sqrt(2.0 / n_mels) * np.cos(math.pi * k * (m + 0.5) / n_mels)
+    d[k[:, 0] == 0] *= math.sqrt(0.5)
+    return d
+
+
+_MCD_TABLES = {}
+
+
+def mcd_table(sample_rate, device):
+    """The parameters and tables of a swc_cepstra call at sample_rate on one device, built once and kept: W and H of
+    mcd_params, 80 Slaney filters (mel_filterbank, pack_filterbanks) and the DCT rows 1 .. 13, built in float64 and rounded to
+    f32 once: the `table` of ops.cepstra."""
+    def build(device):
+        W, H = mcd_params(sample_rate)
+        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, MCD_MELS)])
+        t = {"W": W, "H": H, "n_mels": MCD_MELS, "K": MCD_COEFFS, "sample_rate": int(sample_rate)}
+        for name, v in (("first", first), ("count", count), ("off", off), ("w", w),
+                        ("dct", dct_matrix(MCD_COEFFS, MCD_MELS).astype(np.float32))):
+            t[name] = torch.from_numpy(v).to(device)
+        return t
+    return _cached(_MCD_TABLES, sample_rate, device, build)
+
+
+def mcd_band(sample_rate, band_ms):
+    """r of a swc_dtw call: round(band_ms / hop_ms), 0 (no band) for None.  SwcError below one hop"""
+    if band_ms is None:
+        return 0
+    _, H = mcd_params(sample_rate)
+    try:
+        ms = float(band_ms)
+    except (TypeError, ValueError):
+        raise SwcError(f"mcd: band_ms={band_ms!r}")
+    hop_ms = 1000.0 * H / int(sample_rate)
+    if not (hop_ms <= ms < math.inf):
+        raise SwcError(f"mcd: band_ms={band_ms!r}: None, or at least one hop ({hop_ms:g} ms)")
+    return int(round(ms / hop_ms))
+
+
+def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=False, align=None, max_lag_ms=50.0,
+        device=torch.device("cuda")):
+    """Mel-cepstral distortion of pair i = (ref_list[i] clean, deg_list[i] degraded) in dB, in one swc_cepstra call over the 2 B
+    rows and one swc_dtw call (include/swc_mcd.h): 13 cepstral coefficients (c0 left out) of 80 mel bands, a frame every 10 ms.
+    dtw=True warps the frames of one row onto the other's by exact dynamic time warping (MCD-DTW: for output that stretches and
+    shrinks locally: another vocoder, a TTS or VC system, packet-loss concealment) and the two rows keep their own lengths;
+    dtw=False compares frame t with frame t over the shorter row (plain MCD).  band_ms: a Sakoe-Chiba band of that many
+    milliseconds around the straight line between the corners (None: no band).  -> dict on `device`: "mcd" FloatTensor[B] (NaN
+    for an empty pair), "frames_ref", "frames_deg", "steps" IntTensor[B] (the length of the path) and, with path=True, "path"
+    IntTensor[B][frames_ref + frames_deg - 1 at most][2], the cells (frame of ref, frame of deg) of the path (entries from
+    steps[i] on are 0).  Nothing is synchronised.  align = "waveform" or "envelope": the pairs' constant delay is removed first
+    (aligned(): one small read-back) and "lag" IntTensor[B] added."""
+    state = {}
+
+    def check():
+        W, H = mcd_params(sample_rate)
+        state["band"] = mcd_band(sample_rate, band_ms)
+        for r in list(ref_list) + list(deg_list):
+            if 1 + r.numel() // H > MAX_FRAMES:
+                raise SwcError(f"mcd: a row of {r.numel()} samples is {1 + r.numel() // H} frames: at most MAX_FRAMES = {MAX_FRAMES} "
+                               "(SWC_DTW_MAX_FRAMES of include/swc_mcd.h); score it in pieces")
+
+    def score(ref_list, deg_list, device):
+        B = len(ref_list)
+        if B == 0:
+            res = {"mcd": torch.zeros(0, device=device)}
+            res.update({k: torch.zeros(0, device=device, dtype=torch.int32) for k in ("frames_ref", "frames_deg", "steps")})
+            if path:
+                res["path"] = torch.zeros((0, 0, 2), device=device, dtype=torch.int32)
+            return res
+        table = mcd_table(sample_rate, device)
+        with torch.cuda.device(device):
+            x_rows, y_rows = _stage(ref_list, deg_list, device, cut=False)
+            c = ops.cepstra(x_rows + y_rows, table, ldf=16)
+            r = ops.dtw(c["cep"][:B], c["cep"][B:], c["frames"][:B], c["frames"][B:], D=MCD_COEFFS, band=state["band"],
+                        mode="warp" if dtw else "diagonal", want=("info", "mean") + (("path",) if path else ()))
+            res = {"mcd": r["mean"] * MCD_DB, "frames_ref": r["info"][:, 1], "frames_deg": r["info"][:, 2], "steps": r["info"][:, 0]}
+        if path:
+            res["path"] = r["path"]
+        return res
+    return _scored("mcd", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=check)
+
+
+def dtw(feat_ref, feat_deg, band=0, device=torch.device("cuda")):
+    """Exact DTW of caller-supplied features (swc_dtw on any matrices): feat_ref / feat_deg = lists of 2-D tensors [T_i][D], one
+    D <= 32 for all.  -> dict on `device`: "mean" FloatTensor[B] (the mean Euclidean distance per path step, after the
+    quantisation of include/swc_mcd.h; NaN for an empty pair), "total" LongTensor[B], "steps" IntTensor[B], "path"
+    IntTensor[B][..][2].  Nothing is synchronised."""
+    device = _pairs_on("dtw", feat_ref, feat_deg, _cuda("dtw", "the warping is a HIP kernel", device))
+    B = len(feat_ref)
+    if B == 0:
+        return {"mean": torch.zeros(0, device=device), "total": torch.zeros(0, device=device, dtype=torch.int64),
+                "steps": torch.zeros(0, device=device, dtype=torch.int32), "path": torch.zeros((0, 0, 2), device=device, dtype=torch.int32)}
+    D = feat_ref[0].shape[-1] if feat_ref[0].dim() == 2 else -1
+    if any(f.dim() != 2 or f.shape[1] != D for f in list(feat_ref) + list(feat_deg)) or not 1 <= D <= _lib.DTW_MAX_D:
+        raise SwcError(f"dtw: every feature matrix is [T][D] with one D in 1..{_lib.DTW_MAX_D}")
+    tx, ty = [f.shape[0] for f in feat_ref], [f.shape[0] for f in feat_deg]
+    if max(tx + ty) > MAX_FRAMES:
+        raise SwcError(f"dtw: a matrix of {max(tx + ty)} frames: at most MAX_FRAMES = {MAX_FRAMES} (SWC_DTW_MAX_FRAMES of include/swc_mcd.h)")
+    with torch.cuda.device(device):
+        xf = torch.zeros((B, max(tx), D), device=device)
+        yf = torch.zeros((B, max(ty), D), device=device)
+        for b in range(B):
+            xf[b, :tx[b]] = feat_ref[b].to(device=device, dtype=torch.float32)
+            yf[b, :ty[b]] = feat_deg[b].to(device=device, dtype=torch.float32)
+        counts = torch.tensor(tx + ty, dtype=torch.int32).to(device, non_blocking=True)
+        r = ops.dtw(xf, yf, counts[:B], counts[B:], band=band, want=("total", "info", "mean", "path"))
+    return {"mean": r["mean"], "total": r["total"], "steps": r["info"][:, 0], "path": r["path"]}

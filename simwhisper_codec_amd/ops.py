@@ -889,6 +889,106 @@ def align(x_rows, y_rows, L, mode, want=("info", "values"), max_nx=None, max_ny=
     return res
 
 
+CEPSTRA_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
+DTW_OUTPUTS = ("total", "info", "mean", "path")
+DTW_MODES = {"warp": _lib.DTW_WARP, "diagonal": _lib.DTW_DIAGONAL}
+
+
+def cepstra_frames(n, H):
+    """T of a row of n samples at hop H: 1 + n // H, 0 for an empty row"""
+    return 1 + n // H if n > 0 else 0
+
+
+def cepstra_workspace_bytes(R, max_n_in, W, H):
+    """swc_cepstra_workspace_bytes of include/swc_mcd.h (0: the call keeps every intermediate in LDS)"""
+    v = int(_lib.load().swc_cepstra_workspace_bytes(int(R), int(max_n_in), int(W), int(H)))
+    if v < 0:
+        raise _lib.SwcError(f"cepstra: no workspace size for R={R}, max_n_in={max_n_in}, W={W}, H={H}")
+    return v
+
+
+def cepstra(rows, table, max_n_in=None, ldf=None, out=None, workspace=None):
+    """The mel cepstra of a ragged batch of rows in one call (include/swc_mcd.h swc_cepstra): rows = a list of 1-D f32 device
+    tensors (either side of a pair); `table` = the parameters and the packed tables (metrics.mcd_table: "W", "H", "n_mels", "K"
+    host numbers, "first", "count", "off" int32, "w" f32 and "dct" f32 [K][n_mels] device tensors).  -> dict: "cep" f32
+    [R][T_max][ldf] with T_max = 1 + max_n_in // H (entries with t >= T of a row or k >= K are not written: the tensor comes
+    from torch.zeros), "frames" int32 [R], and "counts" = the host's list of T per row.  max_n_in, ldf, out, workspace (tests):
+    the host's length bound, the row stride of a frame, a dict of output tensors to write and a 256-byte aligned uint8
+    workspace to use instead."""
+    lib = _lib.load()
+    n_in, _, device = _pair_rows("cepstra", rows, None, equal_lengths=False, y_optional=True)
+    R = len(n_in)
+    W, H, M, K = (int(table[k]) for k in ("W", "H", "n_mels", "K"))
+    for name in ("first", "count", "off"):
+        _chk(table[name], f"cepstra table {name}", torch.int32)
+        if table[name].numel() != M or not table[name].is_contiguous():
+            raise _lib.SwcError(f"cepstra: table {name} holds one contiguous entry per filter")
+    _chk(table["w"], "cepstra table w", torch.float32)
+    _chk(table["dct"], "cepstra table dct", torch.float32)
+    if not table["w"].is_contiguous() or not table["dct"].is_contiguous() or table["dct"].numel() != K * M:
+        raise _lib.SwcError("cepstra: the table's weights are contiguous, and dct holds K x n_mels entries")
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    ldf = K if ldf is None else int(ldf)
+    workspace = _workspace("cepstra", cepstra_workspace_bytes(R, max_n, W, H), workspace, device)
+    t_max = 1 + max_n // max(H, 1)
+    res = _outputs("cepstra", {"cep": ((R, t_max, ldf), torch.float32), "frames": ((R,), torch.int32)}, out, device, torch.zeros)
+    xp, n = _row_table(device, [r.data_ptr() for r in rows], n_in)
+    _lib.check(lib.swc_cepstra(_ptr(xp), _ptr(n), max_n, W, H, M, _ptr(table["first"]), _ptr(table["count"]), _ptr(table["off"]),
+                               _ptr(table["w"]), table["w"].numel(), _ptr(table["dct"]), K, _ptr(res["cep"]), ldf, _ptr(res["frames"]),
+                               _ptr(workspace), workspace.numel(), R, _stream()), "swc_cepstra")
+    res["counts"] = [cepstra_frames(min(v, max_n), H) for v in n_in]
+    return res
+
+
+def dtw_workspace_bytes(B, tmax_x, tmax_y, with_path):
+    """swc_dtw_workspace_bytes of include/swc_mcd.h"""
+    v = int(_lib.load().swc_dtw_workspace_bytes(int(B), int(tmax_x), int(tmax_y), int(bool(with_path))))
+    if v < 0:
+        raise _lib.SwcError(f"dtw: no workspace size for B={B}, Tmax_x={tmax_x}, Tmax_y={tmax_y}")
+    return v
+
+
+def dtw(xf, yf, tx, ty, D=None, band=0, mode="warp", want=("total", "info", "mean"), ldp=None, out=None, workspace=None):
+    """The exact DTW (mode "warp") or the diagonal (mode "diagonal") of every feature pair of a batch in one call
+    (include/swc_mcd.h swc_dtw): xf f32 [B][Tmax_x][ldf], yf f32 [B][Tmax_y][ldf] contiguous device tensors, tx / ty int32 [B]
+    device tensors of frame counts, D <= ldf the features compared (default ldf), band = r >= 0.  -> dict of the wanted
+    outputs: total int64 [B], info int32 [B][4] = N, Tx, Ty, e, mean f32 [B], path int32 [B][ldp][2] (entries at and beyond N
+    are not written: the tensor comes from torch.zeros).  ldp, out, workspace (tests): the row stride of path, a dict of output
+    tensors to write and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    want = _want("dtw", want, DTW_OUTPUTS)
+    if mode not in DTW_MODES:
+        raise _lib.SwcError(f"dtw: mode={mode!r}: one of {tuple(DTW_MODES)}")
+    for name, t in (("xf", xf), ("yf", yf)):
+        _chk(t, f"dtw {name}", torch.float32)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise _lib.SwcError(f"dtw: {name} is a contiguous [B][Tmax][ldf] tensor")
+    B, tmax_x, ldf = xf.shape
+    if yf.shape[0] != B or yf.shape[2] != ldf or B == 0:
+        raise _lib.SwcError(f"dtw: xf {tuple(xf.shape)} and yf {tuple(yf.shape)}: one non-zero B and one ldf expected")
+    tmax_y = yf.shape[1]
+    for name, t in (("tx", tx), ("ty", ty)):
+        _chk(t, f"dtw {name}", torch.int32)
+        if t.numel() != B or not t.is_contiguous():
+            raise _lib.SwcError(f"dtw: {name} holds one contiguous frame count per pair")
+    D = ldf if D is None else int(D)
+    band = int(band)
+    if not (1 <= D <= min(ldf, _lib.DTW_MAX_D)) or band < 0:
+        raise _lib.SwcError(f"dtw: D={D} (1..{min(ldf, _lib.DTW_MAX_D)}), band={band} (>= 0)")
+    if max(tmax_x, tmax_y) > _lib.DTW_MAX_FRAMES:
+        raise _lib.SwcError(f"dtw: {tmax_x} and {tmax_y} frames: at most DTW_MAX_FRAMES = {_lib.DTW_MAX_FRAMES} (include/swc_mcd.h)")
+    steps = tmax_x + tmax_y - 1 if tmax_x > 0 and tmax_y > 0 else 0
+    ldp = steps if ldp is None else int(ldp)
+    workspace = _workspace("dtw", dtw_workspace_bytes(B, tmax_x, tmax_y, "path" in want), workspace, xf.device)
+    shapes = {"total": ((B,), torch.int64), "info": ((B, _lib.DTW_INFO), torch.int32), "mean": ((B,), torch.float32),
+              "path": ((B, ldp, 2), torch.int32)}
+    res = _outputs("dtw", {name: shapes[name] for name in want}, out, xf.device, torch.zeros)   # path beyond N is not written
+    _lib.check(lib.swc_dtw(_ptr(xf), _ptr(yf), _ptr(tx), _ptr(ty), tmax_x, tmax_y, D, ldf, band, DTW_MODES[mode], _ptr(res.get("total")),
+                           _ptr(res.get("info")), _ptr(res.get("mean")), _ptr(res.get("path")), ldp, _ptr(workspace), workspace.numel(),
+                           B, _stream()), "swc_dtw")
+    return res
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""
