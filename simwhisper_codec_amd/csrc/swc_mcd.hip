@@ -1,11 +1,10 @@
 // swc_cepstra and swc_dtw (include/swc_mcd.h): mel cepstra of a ragged batch of rows, and the exact DTW of a batch of feature
 // pairs.  No workgroup waits for another.
-//   cepstra_frames_kernel<W>  the frame kernel of swc_spectral.hip for ONE signal and any hop (its FFT in LDS is copied here:
-//                             swc_spectral's device code stays as it is): a workgroup of 256 threads takes a run of 32768 / W
-//                             consecutive frames of one row, a team of min(W / 2, 256) threads owns a frame.  Per frame: the
-//                             windowed frame, W / 2 complex points in bit-reversed order, radix-2 butterflies in place,
-//                             W / 2 + 1 magnitudes, then thread m the m-th mel sum and its logarithm into LDS, then thread k
-//                             the k-th cepstral coefficient: every sum sequential in one thread, one fmaf per term.
+//   cepstra_frames_kernel<W>  the frame kernel of swc_spectral.hip for ONE signal and any hop (geometry, tables, FFT in LDS and
+//                             mel band are swc_frame_fft.h, which both include): a workgroup of 256 threads takes a run of
+//                             32768 / W consecutive frames of one row, a team of min(W / 2, 256) threads owns a frame.  Per
+//                             frame: its W / 2 + 1 magnitudes, then thread m the m-th mel sum and its logarithm into LDS, then
+//                             thread k the k-th cepstral coefficient: every sum sequential in one thread, one fmaf per term.
 //   dtw_peak_kernel           max |v| over both sides of a pair as an unsigned maximum over bit patterns, one atomic per workgroup.
 //   dtw_quant_kernel          both sides as int16 against the pair's one scale, 32 per frame (zero from column D on), in the workspace.
 //   dtw_dp_kernel<G>          one workgroup of 256 threads per pair walks the cost matrix in strips of SWC_DTW_STRIP = 256 rows,
@@ -22,30 +21,18 @@
 //                             direction bits from the end and writes the N cells.
 // Everything up to the one division of `mean` is integer arithmetic.  Every store to global memory is an ordinary vector store
 // from plain C++; the only atomic is the unsigned maximum of the peak.
-#include "swc_metric_common.h"
+#include "swc_frame_fft.h"
 #include "swc_mcd.h"
 
 namespace {
 
 // ---------------------------------------------------------------- swc_cepstra ----
 
-constexpr int CP_THREADS = 256;
-constexpr int CP_RUN_SAMPLES = 32768;  // W * frames of a run
+constexpr int CP_THREADS = FR_THREADS;
+constexpr int CP_RUN_SAMPLES = FR_RUN_SAMPLES;  // W * frames of a run
 constexpr float CP_CLAMP = SWC_CEPSTRA_CLAMP;
 
-bool valid_window(int w) { return w >= 32 && w <= 2048 && (w & (w - 1)) == 0; }
-
 __device__ __forceinline__ float clamp_floor(float v) { return v < CP_CLAMP ? CP_CLAMP : v; }  // NaN stays NaN
-
-template <int W>
-struct Geo {
-    static constexpr int N = W / 2, F = W / 2 + 1;
-    static constexpr int TS = N < CP_THREADS ? N : CP_THREADS;  // threads that own a frame
-    static constexpr int TEAMS = CP_THREADS / TS;               // frames in flight
-    static constexpr int R = CP_RUN_SAMPLES / W;                // frames of a run
-    static constexpr int LOGN = __builtin_ctz(N);
-    static_assert(R % TEAMS == 0 && TS * TEAMS == CP_THREADS, "a run is a whole number of passes");
-};
 
 // grid (runs, R rows)
 template <int W>
@@ -54,8 +41,8 @@ __global__ __launch_bounds__(CP_THREADS) void cepstra_frames_kernel(
     const int32_t* __restrict__ fb_first, const int32_t* __restrict__ fb_count, const int32_t* __restrict__ fb_off,
     const float* __restrict__ fb_w, long fb_w_len, const float* __restrict__ dct, int K, float* __restrict__ cep, long ldf,
     long t_max, int32_t* __restrict__ frames) {
-    using G = Geo<W>;
-    constexpr int N = G::N, F = G::F, TS = G::TS, TEAMS = G::TEAMS, R = G::R, LOGN = G::LOGN;
+    using G = FrameGeo<W>;
+    constexpr int N = G::N, F = G::F, TS = G::TS, TEAMS = G::TEAMS, R = G::R;
     __shared__ float2 s_tw[N];  // exp(-2 pi i q / W)
     __shared__ float s_win[W];
     __shared__ float2 s_z[TEAMS][N];
@@ -69,65 +56,18 @@ __global__ __launch_bounds__(CP_THREADS) void cepstra_frames_kernel(
     const long t0 = (long)blockIdx.x * R;
     if (t0 >= T) return;
     const int nfr = (int)(T - t0 < R ? T - t0 : R);
-    const float* p = reinterpret_cast<const float*>(rows[b]);
-    for (int q = tid; q < N; q += CP_THREADS) {
-        double sn, cs;
-        sincospi(-2.0 * (double)q / (double)W, &sn, &cs);
-        s_tw[q] = make_float2((float)cs, (float)sn);
-    }
-    for (int i = tid; i < W; i += CP_THREADS) s_win[i] = (float)(0.5 - 0.5 * cospi(2.0 * (double)i / (double)W));
-    __syncthreads();
+    const float* row[1] = {reinterpret_cast<const float*>(rows[b])};
+    frame_tables<W>(s_tw, s_win, tid);
 
     for (int pass = 0; pass * TEAMS < nfr; ++pass) {  // (uniform: every team takes part in every barrier)
         const int r = pass * TEAMS + team;
         const bool active = r < nfr;                  // a team past the row's last frame works on zeros and stores nothing
         const long start = (t0 + r) * (long)H - N;    // the frame's first sample
-        // the windowed frame, packed z[k] = v[2 k] + i v[2 k + 1], stored where the in-place transform wants it
-        for (int k = lt; k < N; k += TS) {
-            const long i0 = start + 2 * k;
-            const float v0 = (active && i0 >= 0 && i0 < n) ? p[i0] * s_win[2 * k] : 0.0f;
-            const float v1 = (active && i0 + 1 >= 0 && i0 + 1 < n) ? p[i0 + 1] * s_win[2 * k + 1] : 0.0f;
-            s_z[team][__brev((unsigned)k) >> (32 - LOGN)] = make_float2(v0, v1);
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int lh = 0; lh < LOGN; ++lh) {
-            const int h = 1 << lh;
-            for (int j = lt; j < N / 2; j += TS) {
-                const int k = j & (h - 1), a = ((j >> lh) << (lh + 1)) + k;
-                const float2 w = s_tw[k << (LOGN - lh)];  // exp(-2 pi i k / (2 h))
-                float2* z = s_z[team];
-                const float2 u = z[a], v = z[a + h];
-                const float tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
-                z[a] = make_float2(u.x + tr, u.y + ti);
-                z[a + h] = make_float2(u.x - tr, u.y - ti);
-            }
-            __syncthreads();
-        }
-        // unpack: with A = Z[f], Bc = conj Z[N - f]: E = (A + Bc) / 2, O = -i (A - Bc) / 2, P = tw[f] O;
-        // |X[f]| = |E + P|, |X[N - f]| = |E - P|, f = 0 .. N / 2
-        for (int f = lt; f < N / 2 + 1; f += TS) {
-            const float2* z = s_z[team];
-            const float2 A = z[f], B = z[(N - f) & (N - 1)], w = s_tw[f];
-            const float er = 0.5f * (A.x + B.x), ei = 0.5f * (A.y - B.y);
-            const float orr = 0.5f * (A.y + B.y), oi = -0.5f * (A.x - B.x);
-            const float pr = w.x * orr - w.y * oi, pi = w.x * oi + w.y * orr;
-            const float ar = er + pr, ai = ei + pi, br = er - pr, bi = ei - pi;
-            s_mag[team][f] = sqrtf(ar * ar + ai * ai);
-            s_mag[team][N - f] = sqrtf(br * br + bi * bi);
-        }
-        __syncthreads();
-        const float* mx = s_mag[team];
+        frame_magnitudes<W, 1>(row, n, start, active, lt, s_tw, s_win, &s_z[team], &s_mag[team]);
         for (int m = lt; m < M; m += TS) {
-            const long first = fb_first[m], cnt = fb_count[m], off = fb_off[m];
-            const long lo = first < 0 ? 0 : first, hi = first + cnt < F ? first + cnt : F;  // cut into [0, F)
-            float a = 0.0f;
-            for (long f = lo; f < hi; ++f) {
-                const long wi = off + (f - first);
-                if (wi < 0 || wi >= fb_w_len) continue;  // cut into the weight array
-                a = fmaf(fb_w[wi], mx[f], a);
-            }
-            s_log[team][m] = logf(clamp_floor(a));
+            float a[1];
+            mel_band<F, 1>(fb_first[m], fb_count[m], fb_off[m], fb_w, fb_w_len, &s_mag[team], a);
+            s_log[team][m] = logf(clamp_floor(a[0]));
         }
         __syncthreads();
         for (int k = lt; k < K; k += TS) {

@@ -1,4 +1,4 @@
-// What the metric calls share (swc_stoi.hip, swc_spectral.hip, swc_pitch.hip, swc_align.hip): the workspace rounding, the
+// What the metric calls share (swc_stoi.hip, swc_spectral.hip, swc_pitch.hip, swc_align.hip, swc_mcd.hip): the workspace rounding, the
 // clamp of a row's length, the int16 quantisation against a row's peak and the packed 16-bit dot product.  Helpers only: no
 // kernel lives here, and nothing is a template over its callers.
 //

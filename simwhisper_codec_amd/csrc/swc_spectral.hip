@@ -1,36 +1,29 @@
 // swc_spectral (include/swc_spectral.h): multi-scale mel, multi-resolution STFT and log-spectral distance of a ragged batch
 // of pairs.  Two kinds of launch, no workgroup waits for another:
 //   spectral_frames_kernel<W>  one per scale with work.  A workgroup of 256 threads takes one run of SWC_SPECTRAL_RUN_<W>
-//                              consecutive frames of one row.  A TEAM of TS = min(W / 2, 256) threads owns a frame (a quarter
-//                              of a wave at W = 32, a wave at W = 128, the workgroup from W = 512 on), so 256 / TS frames are in
-//                              flight per pass.  Per frame: the two windowed frames are loaded (zero outside [0, n), nothing
-//                              outside the row is read), each packed into W / 2 complex points in bit-reversed order, transformed
-//                              in place in LDS by the same radix-2 butterflies (the work index carries the signal, so x and y go
-//                              through the same instructions), unpacked into W / 2 + 1 magnitudes, and reduced to four f32 sums
-//                              in a fixed order.  What a frame computes does not depend on its place in the run: its four sums
-//                              go to an LDS slot of their own, and four threads add the slots in frame order in float64 into
-//                              the record of the run.
+//                              consecutive frames of one row, a team of min(W / 2, 256) threads owns a frame; the magnitudes
+//                              of the frame's two signals come from swc_frame_fft.h (geometry, tables, FFT in LDS, mel band:
+//                              shared with swc_mcd.hip).  At W = 256 alone the load, FFT and unpack stay written out here:
+//                              through the header the same instructions are scheduled differently there and that scale takes
+//                              0.023 ms (4.9 %) longer; the other six windows do not change (profiles/frame_fft_ab.txt).  A
+//                              change to frame_magnitudes is made in that copy too; tests/test_frame_bits_gpu.py holds both to
+//                              their bits.  The magnitudes are reduced to four f32 sums in a fixed order.  What a frame
+//                              computes does not depend on its place in the run: its four sums go to an LDS slot of their
+//                              own, and four threads add the slots in frame order in float64 into the record of the run.
 //   spectral_finish_kernel     one workgroup per row adds the run records of every scale in ascending order in float64 (loads
 //                              in parallel, adds in order, as sisdr_finish_kernel), divides, sums the scales and rounds once.
-// Twiddles exp(-2 pi i q / W), q < W / 2, and the window are evaluated in float64 (sincospi / cospi) once per workgroup and
-// kept in LDS as f32; the FFT stages and the unpacking both read that one table.
-// LDS banking: a butterfly reads two float2 (ds_read_b64, 64 banks); from half-size 32 on a team's lanes read consecutive
-// float2 (conflict-free), the first five stages read with a stride of 2 .. 32 float2 between pairs of lanes (2-way).
-#include "swc_metric_common.h"
-#include "swc_spectral.h"
+#include "swc_frame_fft.h"
 
 namespace {
 
-constexpr int SP_THREADS = 256;
-constexpr int SP_RUN_SAMPLES = 32768;  // W * SWC_SPECTRAL_RUN_<W>
+constexpr int SP_THREADS = FR_THREADS;
+constexpr int SP_RUN_SAMPLES = FR_RUN_SAMPLES;  // W * SWC_SPECTRAL_RUN_<W>
 constexpr float SP_CLAMP = 1e-5f;
 static_assert(SWC_SPECTRAL_RUN_32 * 32 == SP_RUN_SAMPLES && SWC_SPECTRAL_RUN_64 * 64 == SP_RUN_SAMPLES &&
                   SWC_SPECTRAL_RUN_128 * 128 == SP_RUN_SAMPLES && SWC_SPECTRAL_RUN_256 * 256 == SP_RUN_SAMPLES &&
                   SWC_SPECTRAL_RUN_512 * 512 == SP_RUN_SAMPLES && SWC_SPECTRAL_RUN_1024 * 1024 == SP_RUN_SAMPLES &&
                   SWC_SPECTRAL_RUN_2048 * 2048 == SP_RUN_SAMPLES,
               "every run length is 32768 / W");
-
-bool valid_window(int w) { return w >= SWC_SPECTRAL_MIN_WIN && w <= SWC_SPECTRAL_MAX_WIN && (w & (w - 1)) == 0; }
 
 // what the finish kernel needs to know about the scales (passed by value)
 struct Scales {
@@ -41,17 +34,6 @@ struct Scales {
 };
 
 __device__ __forceinline__ float clamp_floor(float v) { return v < SP_CLAMP ? SP_CLAMP : v; }  // NaN stays NaN
-
-template <int W>
-struct Geo {
-    static constexpr int N = W / 2, F = W / 2 + 1, H = W / 4;
-    static constexpr int TS = N < SP_THREADS ? N : SP_THREADS;  // threads that own a frame
-    static constexpr int TEAMS = SP_THREADS / TS;               // frames in flight
-    static constexpr int TW = TS < 64 ? 1 : TS / 64;            // waves of a team
-    static constexpr int R = SP_RUN_SAMPLES / W;                // frames of a run
-    static constexpr int LOGN = __builtin_ctz(N);
-    static_assert(R % TEAMS == 0 && TS * TEAMS == SP_THREADS, "a run is a whole number of passes");
-};
 
 // the sum of v over the TS threads of a team, the same value in each of them, in one fixed order: an xor butterfly inside the
 // wave, then the team's waves in ascending order through LDS.  Every thread of the workgroup calls it
@@ -84,8 +66,8 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_frames_kernel(
     const void* const* __restrict__ x_rows, const void* const* __restrict__ y_rows, const int64_t* __restrict__ n_in, long max_n,
     int eff, int M, int fb_base, const int32_t* __restrict__ fb_first, const int32_t* __restrict__ fb_count,
     const int32_t* __restrict__ fb_off, const float* __restrict__ fb_w, long fb_w_len, double* __restrict__ rec, long runs) {
-    using G = Geo<W>;
-    constexpr int N = G::N, F = G::F, H = G::H, TS = G::TS, TEAMS = G::TEAMS, TW = G::TW, R = G::R, LOGN = G::LOGN;
+    using G = FrameGeo<W>;
+    constexpr int N = G::N, F = G::F, H = W / 4, TS = G::TS, TEAMS = G::TEAMS, TW = G::TW, R = G::R, LOGN = G::LOGN;
     __shared__ float2 s_tw[N];              // exp(-2 pi i q / W)
     __shared__ float s_win[W];
     __shared__ float2 s_z[TEAMS][2][N];     // [team][x, y]
@@ -99,57 +81,55 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_frames_kernel(
     if (t0 >= T) return;
     const int nfr = (int)(T - t0 < R ? T - t0 : R);
     const float* rows[2] = {reinterpret_cast<const float*>(x_rows[b]), reinterpret_cast<const float*>(y_rows[b])};
-    for (int q = tid; q < N; q += SP_THREADS) {
-        double sn, cs;
-        sincospi(-2.0 * (double)q / (double)W, &sn, &cs);
-        s_tw[q] = make_float2((float)cs, (float)sn);
-    }
-    for (int i = tid; i < W; i += SP_THREADS) s_win[i] = (float)(0.5 - 0.5 * cospi(2.0 * (double)i / (double)W));
-    __syncthreads();
+    frame_tables<W>(s_tw, s_win, tid);
 
     for (int pass = 0; pass * TEAMS < nfr; ++pass) {  // (uniform: every team takes part in every barrier)
         const int r = pass * TEAMS + team;
         const bool active = r < nfr;                  // a team past the row's last frame works on zeros and stores nothing
         const long start = (t0 + r) * H - N;          // the frame's first sample
-        // the two windowed frames, packed z[k] = v[2 k] + i v[2 k + 1], stored where the in-place transform wants them
-        for (int i = lt; i < 2 * N; i += TS) {
-            const int sig = i / N, k = i % N;
-            const long i0 = start + 2 * k;
-            const float* p = rows[sig];
-            const float v0 = (active && i0 >= 0 && i0 < n) ? p[i0] * s_win[2 * k] : 0.0f;
-            const float v1 = (active && i0 + 1 >= 0 && i0 + 1 < n) ? p[i0 + 1] * s_win[2 * k + 1] : 0.0f;
-            s_z[team][sig][__brev((unsigned)k) >> (32 - LOGN)] = make_float2(v0, v1);
-        }
-        __syncthreads();
+        if constexpr (W != 256) {
+            frame_magnitudes<W, 2>(rows, n, start, active, lt, s_tw, s_win, s_z[team], s_mag[team]);
+        } else {  // frame_magnitudes<256, 2> written out: inlined from the header this one window is 4.9 % slower
+            // the two windowed frames, packed z[k] = v[2 k] + i v[2 k + 1], stored where the in-place transform wants them
+            for (int i = lt; i < 2 * N; i += TS) {
+                const int sig = i / N, k = i % N;
+                const long i0 = start + 2 * k;
+                const float* p = rows[sig];
+                const float v0 = (active && i0 >= 0 && i0 < n) ? p[i0] * s_win[2 * k] : 0.0f;
+                const float v1 = (active && i0 + 1 >= 0 && i0 + 1 < n) ? p[i0 + 1] * s_win[2 * k + 1] : 0.0f;
+                s_z[team][sig][__brev((unsigned)k) >> (32 - LOGN)] = make_float2(v0, v1);
+            }
+            __syncthreads();
 #pragma unroll 1
-        for (int lh = 0; lh < LOGN; ++lh) {
-            const int h = 1 << lh;
-            for (int i = lt; i < N; i += TS) {  // N / 2 butterflies of x, then N / 2 of y
-                const int sig = i / (N / 2), j = i % (N / 2);
-                const int k = j & (h - 1), a = ((j >> lh) << (lh + 1)) + k;
-                const float2 w = s_tw[k << (LOGN - lh)];  // exp(-2 pi i k / (2 h))
-                float2* z = s_z[team][sig];
-                const float2 u = z[a], v = z[a + h];
-                const float tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
-                z[a] = make_float2(u.x + tr, u.y + ti);
-                z[a + h] = make_float2(u.x - tr, u.y - ti);
+            for (int lh = 0; lh < LOGN; ++lh) {
+                const int h = 1 << lh;
+                for (int i = lt; i < N; i += TS) {  // N / 2 butterflies of x, then N / 2 of y
+                    const int sig = i / (N / 2), j = i % (N / 2);
+                    const int k = j & (h - 1), a = ((j >> lh) << (lh + 1)) + k;
+                    const float2 w = s_tw[k << (LOGN - lh)];  // exp(-2 pi i k / (2 h))
+                    float2* z = s_z[team][sig];
+                    const float2 u = z[a], v = z[a + h];
+                    const float tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
+                    z[a] = make_float2(u.x + tr, u.y + ti);
+                    z[a + h] = make_float2(u.x - tr, u.y - ti);
+                }
+                __syncthreads();
+            }
+            // unpack: with A = Z[f], Bc = conj Z[N - f]: E = (A + Bc) / 2, O = -i (A - Bc) / 2, P = tw[f] O;
+            // |X[f]| = |E + P|, |X[N - f]| = |E - P|, f = 0 .. N / 2
+            for (int i = lt; i < 2 * (N / 2 + 1); i += TS) {
+                const int sig = i / (N / 2 + 1), f = i % (N / 2 + 1);
+                const float2* z = s_z[team][sig];
+                const float2 A = z[f], B = z[(N - f) & (N - 1)], w = s_tw[f];
+                const float er = 0.5f * (A.x + B.x), ei = 0.5f * (A.y - B.y);
+                const float orr = 0.5f * (A.y + B.y), oi = -0.5f * (A.x - B.x);
+                const float pr = w.x * orr - w.y * oi, pi = w.x * oi + w.y * orr;
+                const float ar = er + pr, ai = ei + pi, br = er - pr, bi = ei - pi;
+                s_mag[team][sig][f] = sqrtf(ar * ar + ai * ai);
+                s_mag[team][sig][N - f] = sqrtf(br * br + bi * bi);
             }
             __syncthreads();
         }
-        // unpack: with A = Z[f], Bc = conj Z[N - f]: E = (A + Bc) / 2, O = -i (A - Bc) / 2, P = tw[f] O;
-        // |X[f]| = |E + P|, |X[N - f]| = |E - P|, f = 0 .. N / 2
-        for (int i = lt; i < 2 * (N / 2 + 1); i += TS) {
-            const int sig = i / (N / 2 + 1), f = i % (N / 2 + 1);
-            const float2* z = s_z[team][sig];
-            const float2 A = z[f], B = z[(N - f) & (N - 1)], w = s_tw[f];
-            const float er = 0.5f * (A.x + B.x), ei = 0.5f * (A.y - B.y);
-            const float orr = 0.5f * (A.y + B.y), oi = -0.5f * (A.x - B.x);
-            const float pr = w.x * orr - w.y * oi, pi = w.x * oi + w.y * orr;
-            const float ar = er + pr, ai = ei + pi, br = er - pr, bi = ei - pi;
-            s_mag[team][sig][f] = sqrtf(ar * ar + ai * ai);
-            s_mag[team][sig][N - f] = sqrtf(br * br + bi * bi);
-        }
-        __syncthreads();
         const float* mx = s_mag[team][0];
         const float* my = s_mag[team][1];
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // mel, log-magnitude L1, magnitude L1, squared log difference
@@ -164,17 +144,9 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_frames_kernel(
         }
         if (eff & SWC_SPECTRAL_MEL) {
             for (int m = lt; m < M; m += TS) {
-                const long first = fb_first[fb_base + m], cnt = fb_count[fb_base + m], off = fb_off[fb_base + m];
-                const long lo = first < 0 ? 0 : first, hi = first + cnt < F ? first + cnt : F;  // cut into [0, F)
-                float ax = 0.0f, ay = 0.0f;
-                for (long f = lo; f < hi; ++f) {
-                    const long wi = off + (f - first);
-                    if (wi < 0 || wi >= fb_w_len) continue;  // cut into the weight array
-                    const float w = fb_w[wi];
-                    ax = fmaf(w, mx[f], ax);
-                    ay = fmaf(w, my[f], ay);
-                }
-                v[0] += fabsf(log10f(clamp_floor(ax)) - log10f(clamp_floor(ay)));
+                float a[2];
+                mel_band<F, 2>(fb_first[fb_base + m], fb_count[fb_base + m], fb_off[fb_base + m], fb_w, fb_w_len, s_mag[team], a);
+                v[0] += fabsf(log10f(clamp_floor(a[0])) - log10f(clamp_floor(a[1])));
             }
         }
         team_sum4<TS, TW>(v, s_red[team], lt);
