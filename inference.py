@@ -95,6 +95,15 @@ def build_parser():
                    help="the MD5 signature of --output_format flac files.  device (default): computed on the GPU, one lane "
                         "per file (a serial chain: it can cost more than the compression itself).  none: the field stays "
                         "zero, which FLAC defines as 'no signature'; decoders then skip that check")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="programme loudness to normalise to (EBU R128: -23), on the GPU and single-GPU only.  Default: off, every "
+                        "file is written as before.  --mode roundtrip / encode: every input is brought to that integrated "
+                        "loudness (BS.1770-4) before it is encoded; --mode decode: every decoded waveform is, before it is "
+                        "written.  The gain is computed and applied on the device (AudioCodec.encode(loudness=), "
+                        "metrics.normalised); a file too short or too quiet to measure passes unchanged")
+    p.add_argument("--true_peak_db", type=float, default=-1.0, metavar="DB",
+                   help="with --loudness: the true-peak ceiling in dB relative to full scale; the gain is lowered where the "
+                        "target loudness would exceed it")
     return p
 
 
@@ -186,9 +195,13 @@ def main(argv=None):
     if world > 1 and args.output_format != "wav":
         raise SystemExit(f"--output_format {args.output_format} compresses on one GPU: start it without torch.distributed.run "
                          f"(WORLD_SIZE={world}); data-parallel runs write WAV")
+    if world > 1 and args.loudness is not None:
+        raise SystemExit(f"--loudness normalises on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    if args.loudness is not None and device.type != "cuda":
+        raise SystemExit("--loudness measures and normalises on the GPU: --device must be a CUDA device")
     flac_out = args.output_format == "flac"
     if flac_out and device.type != "cuda":
         raise SystemExit("--output_format flac compresses the output on the GPU: --device must be a CUDA device")
@@ -213,6 +226,7 @@ def main(argv=None):
     stager = HostStager()
 
     on_gpu = device.type == "cuda"
+    level = {} if args.loudness is None else {"loudness": args.loudness, "true_peak_db": args.true_peak_db}
 
     def load_one(path):
         return load_file(path, generator.input_sample_rate, on_gpu, args.resample, args.flac)
@@ -276,7 +290,7 @@ def main(argv=None):
         with torch.no_grad():
             t1 = time.perf_counter()
             def round_trip():
-                codes = model.encode(wav_list, overlap_seconds=10, device=device)["codes_list"]
+                codes = model.encode(wav_list, overlap_seconds=10, device=device, **level)["codes_list"]
                 if to_codes:   # the file images of the batch, packed on the device by one launch (inside the range check)
                     with torch.cuda.device(device):
                         return codes, bitstream.pack_batch(codes)
@@ -407,6 +421,10 @@ def main_decode(args, generator, device):
                                      "(a corrupt file, or codes of another model)")
                 logging.info(f"Successfully loaded {len(views)} code files with lengths {[v.shape[-1] for v in views]} frames")
                 syn = generator.decode(views, overlap_seconds=10, device=device)["syn_wav_list"]
+                if args.loudness is not None:
+                    from simwhisper_codec_amd import metrics
+                    syn = metrics.normalised(syn, generator.output_sample_rate, target_lufs=args.loudness,
+                                             true_peak_db=args.true_peak_db, device=device)[0]
                 lens = [len(w) for w in syn]
                 if flac_out:
                     if pending is not None:   # the images are slices of ONE pinned buffer: the last batch's are written first

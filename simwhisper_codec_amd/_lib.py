@@ -222,6 +222,22 @@ MCD_SIGNATURES = {
     "swc_dtw": ([_P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _L, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_loudness.h (BS.1770 / R128 loudness measures and the device-side normalising gain), one to one.  The eleventh table
+# of its own
+_D = C.c_double
+LOUDNESS_MIN_FS, LOUDNESS_MAX_FS = 8000, 48000   # SWC_LOUDNESS_MIN_FS / _MAX_FS
+LOUDNESS_MAX_N = 1 << 30                         # SWC_LOUDNESS_MAX_N
+LOUDNESS_VALUES = 8                              # SWC_LOUDNESS_VALUES
+LOUDNESS_MAX_WIDTH = 64                          # SWC_LOUDNESS_MAX_WIDTH
+LOUDNESS_GROUP = 64                              # SWC_LOUDNESS_GROUP
+LOUDNESS_UNMEASURED, LOUDNESS_PEAK_LIMITED = 1, 2   # SWC_LOUDNESS_UNMEASURED / _PEAK_LIMITED
+LOUDNESS_SIGNATURES = {
+    "swc_loudness_coefficients": ([_I, C.POINTER(_D)], C.c_int),
+    "swc_loudness_workspace_bytes": ([_I, _L, _I], C.c_int64),
+    "swc_loudness": ([_P, _P, _L, _I, _I, _P, _P, _I, _P, _P, _L, _I, _P], C.c_int),
+    "swc_loudness_normalise": ([_P, _P, _P, _D, _D, _P, _L, _L, _P, _P, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -241,7 +257,8 @@ def load():
         fn.restype = C.c_int
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
-                  FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES):
+                  FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
+                  LOUDNESS_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

@@ -1234,17 +1234,26 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
-    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
+    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, loudness=None, true_peak_db=-1.0):
         """model.py:244-308: 30 s windows every (30 - overlap) s, keep the first 250 codes of each window,
         concatenate, trim to len // 1280.  Returns {"codes_list": [IntTensor(G, T_i)]}.
         sample_rate: None = the waveforms are at input_sample_rate (the reference's contract).  An int, or one int per
         utterance: the rate of each row; rows at another rate are converted on the GPU first (ops.resample, the whole row,
-        then windowed as usual), so row i yields ceil(input_sample_rate n_i / sr_i) // 1280 code frames."""
+        then windowed as usual), so row i yields ceil(input_sample_rate n_i / sr_i) // 1280 code frames.
+        loudness: None = the rows as given.  A number: every row is first brought to that integrated loudness (LUFS, EBU R128:
+        -23) under a true-peak ceiling of true_peak_db, at input_sample_rate and on the GPU (metrics.normalised: the gain is
+        computed and applied on the device, nothing is read back, so it composes with deferred_range_check())."""
         B = len(wav_list)
         if B == 0:
             return {"codes_list": []}
         if sample_rate is not None:
             wav_list = self._to_input_rate(wav_list, sample_rate, self._resolve_device(device))
+        if loudness is not None:
+            from . import metrics
+            dev = self._resolve_device(device)
+            if dev.type != "cuda":
+                raise SwcError("encode(loudness=): the meter is a HIP kernel (there is no CPU fallback)")
+            wav_list = metrics.normalised(wav_list, self.input_sample_rate, target_lufs=loudness, true_peak_db=true_peak_db, device=dev)[0]
         n = [int(w.shape[-1]) if w.dim() else 0 for w in wav_list]
         dev = self._resolve_device(device)
         # Rows are independent, so the batch is assembled longest utterance first: workgroups are dispatched row by row
@@ -1480,6 +1489,28 @@ class AudioCodec(nn.Module):
             y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
             syn = [y[k, : n_out[k]] for k in range(len(syn))]
         return metrics.pitch(wav_list, syn, sample_rate=self.input_sample_rate, f_min=f_min, f_max=f_max, device=dev, tracks=tracks)
+
+    @_on_model_device
+    @torch.inference_mode()
+    def loudness(self, wav_list, overlap_seconds=10, device=torch.device("cuda")):
+        """quality() for the loudness numbers: encode -> decode -> metrics.loudness of the input and of the reconstruction (at
+        input_sample_rate).  -> dict on the model's device: "ref" and "deg", each the dict of metrics.loudness, and
+        "integrated_diff", "range_diff", "true_peak_db_diff" (deg - ref, float64 [B]; NaN where either side is)."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("loudness: the meter is a HIP kernel (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        ref = metrics.loudness(wav_list, sample_rate=self.input_sample_rate, device=dev)
+        deg = metrics.loudness(syn, sample_rate=self.input_sample_rate, device=dev)
+        res = {"ref": ref, "deg": deg}
+        for k in ("integrated", "range", "true_peak_db"):
+            res[k + "_diff"] = deg[k] - ref[k]
+        return res
 
     @_on_model_device
     @torch.inference_mode()

@@ -30,6 +30,13 @@ vocoder papers print from the two tracks.
 find the constant delay of every pair before it is scored (include/swc_align.h): an exact int64 cross-correlation over
 +- max_lag_ms, of the waveform or of its rectified envelope.  Every metric above assumes sample-aligned rows; `align=` makes
 them usable on the output of another codec or processing chain.  An aligned pair is two offset views: no audio is copied.
+
+    l = metrics.loudness(wav_list, sample_rate=16000)               # {"integrated", "range", "true_peak_db", ...}
+    rows, gains, flags = metrics.normalised(wav_list, 16000)        # -23 LUFS under -1 dB true peak, no read-back
+    s = metrics.spectral(ref_list, deg_list, level="loudness")      # the degraded rows brought to the clean rows' loudness first
+
+say how loud a row is (include/swc_loudness.h): BS.1770-4 integrated loudness, EBU Tech 3342 loudness range, sample and true
+peak, and the gain that normalises a row, computed and applied on the device.
 """
 import math
 
@@ -272,7 +279,8 @@ def spectral_table(sample_rate, device):
     return _cached(_SPECTRAL_TABLES, sample_rate, device, build)
 
 
-def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0):
+def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0,
+             level=None):
     """Multi-scale mel distance, multi-resolution STFT distance and log-spectral distance of pair i = (ref_list[i] clean,
     deg_list[i] degraded) in one swc_spectral call: the lists, the cut to the shorter length and the staging of host rows are
     those of quality().  `want`: which of "mel", "stft", "lsd".  -> dict on `device`: a FloatTensor[B] per wanted metric,
@@ -280,10 +288,29 @@ def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"),
     or the measure is not wanted) and "scales" = [(W, n_mels, flags)] as computed.  Every value of an empty pair is NaN.  The
     rate enters through the mel banks only: any rate works.  Nothing is synchronised.  align = "waveform" or "envelope": the
     pairs are aligned first (aligned(): one small read-back), their views scored and "lag" IntTensor[B] added; None: the rows
-    as given."""
+    as given.  level = "loudness": the degraded rows are first scaled to the clean rows' integrated loudness (level_matched():
+    no read-back; the rate must then be one swc_loudness takes) and "gain_db" FloatTensor[B] says by how much, so that level and
+    colouration are told apart; None: the rows as given."""
     want = tuple(want)
+    if level not in (None, "loudness"):
+        raise SwcError(f"spectral: level={level!r}: None or 'loudness'")
+    if level is not None:
+        ops.loudness_check_rate(sample_rate)
 
     def score(ref_list, deg_list, device):
+        gain_db = None
+        if level is not None and len(ref_list):
+            ref_list, deg_list = _stage(ref_list, deg_list, device)
+            deg_list, gains = level_matched(ref_list, deg_list, sample_rate, device=device)
+            gain_db = 20.0 * torch.log10(gains)
+        elif level is not None:
+            gain_db = torch.zeros(0, device=device)
+        res = _score(ref_list, deg_list, device)
+        if gain_db is not None:
+            res["gain_db"] = gain_db
+        return res
+
+    def _score(ref_list, deg_list, device):
         table = spectral_table(sample_rate, device)
         mask = sum(ops._SPECTRAL_FLAG[w] for w in want)
         table = dict(table, flags=[f & mask for f in table["flags"]])     # an unwanted measure costs nothing, and is 0 in parts
@@ -447,6 +474,80 @@ def aligned(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="wavefo
     xs = [x[x0:x0 + m] for x, (x0, _, m) in zip(x_rows, cut)]
     ys = [y[y0:y0 + m] for y, (_, y0, m) in zip(y_rows, cut)]
     return xs, ys, res
+
+
+# ---- loudness (include/swc_loudness.h) ----
+
+LOUDNESS_KEYS = ("integrated", "range", "momentary_max", "short_term_max", "sample_peak_db", "true_peak_db", "blocks", "blocks_kept")
+
+
+def _rows(wav_list, device):
+    """the rows of a loudness call as contiguous f32 rows on `device` (the staging of _stage, one list)"""
+    return _stage(wav_list, wav_list, device, cut=False)[0]
+
+
+def _loudness_device(who, sample_rate, device):
+    ops.loudness_check_rate(sample_rate)
+    device = _cuda(who, "the meter is a HIP kernel", device)
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def loudness(wav_list, sample_rate=16000, device=torch.device("cuda"), want=LOUDNESS_KEYS):
+    """How loud every waveform of a list is, in one swc_loudness call (ITU-R BS.1770-4, EBU R128; include/swc_loudness.h): 1-D
+    mono waveforms at sample_rate (a multiple of 10 in 8000 .. 48000; host or device tensors).  `want`: which of LOUDNESS_KEYS.
+    -> dict on `device`, a float64 tensor [B] per key: "integrated" (LUFS, both gates), "range" (LU, EBU Tech 3342),
+    "momentary_max" and "short_term_max" (LUFS over 0.4 s and 3 s), "sample_peak_db" and "true_peak_db" (dB relative to full
+    scale; the true peak is that of the project's own 4 x interpolator), "blocks" and "blocks_kept" (momentary blocks, and
+    those both gates keep).  NaN where a value is not defined (a row under 0.4 s, or all of it under -70 LUFS, has no integrated
+    loudness).  Nothing is synchronised."""
+    want = ops._want("loudness", want, LOUDNESS_KEYS)
+    device = _loudness_device("loudness", sample_rate, device)
+    if len(wav_list) == 0:
+        return {w: torch.zeros(0, device=device, dtype=torch.float64) for w in want}
+    with torch.cuda.device(device):
+        v = ops.loudness(_rows(wav_list, device), sample_rate)
+        cols = {k: v[:, i] for i, k in enumerate(LOUDNESS_KEYS)}
+        for k in ("sample_peak_db", "true_peak_db"):
+            if k in want:
+                cols[k] = 20.0 * torch.log10(cols[k])
+    return {w: cols[w] for w in want}
+
+
+def normalised(wav_list, sample_rate, target_lufs=-23.0, true_peak_db=-1.0, device=torch.device("cuda")):
+    """Every waveform of a list brought to target_lufs integrated loudness, with a gain small enough to keep its true peak under
+    true_peak_db: one swc_loudness and one swc_loudness_normalise call, the gain computed on the device (no read-back, nothing
+    synchronised).  -> (rows, gains, flags): rows = views of ONE zero-padded batch, row i of its waveform's length; gains
+    FloatTensor[B] (linear); flags IntTensor[B], bit 0 = the row has no integrated loudness and is passed through with gain 1,
+    bit 1 = the true-peak ceiling set the gain."""
+    device = _loudness_device("normalised", sample_rate, device)
+    if len(wav_list) == 0:
+        return [], torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        rows = _rows(wav_list, device)
+        out, gains, flags = ops.loudness_normalise(rows, ops.loudness(rows, sample_rate), target_lufs, true_peak_db)
+    return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+
+
+def level_matched(ref_list, deg_list, sample_rate, device=torch.device("cuda")):
+    """The degraded rows scaled to the clean rows' integrated loudness: -> (rows, gains): rows = views of one batch, row i =
+    deg_list[i] * gains[i] with gains[i] = 10^((I_ref - I_deg) / 20) rounded to f32 (one swc_loudness call over the 2 B rows, one
+    swc_loudness_normalise call over the degraded ones: no read-back).  A pair with either side unmeasured (no integrated
+    loudness) has gain 1."""
+    device = _loudness_device("level_matched", sample_rate, device)
+    device = _pairs_on("level_matched", ref_list, deg_list, device)
+    if len(ref_list) == 0:
+        return [], torch.zeros(0, device=device)
+    B = len(ref_list)
+    with torch.cuda.device(device):
+        rows = _rows(list(ref_list) + list(deg_list), device)
+        I = ops.loudness(rows, sample_rate)[:, 0]
+        # swc_loudness_normalise with target 0 on rows whose "integrated loudness" is I_deg - I_ref (NaN when either is) and whose
+        # "true peak" is too small for any ceiling to bind: the gain above, computed and applied by the kernel
+        v = torch.zeros((B, _lib.LOUDNESS_VALUES), device=device, dtype=torch.float64)
+        v[:, 0] = I[B:] - I[:B]
+        v[:, 5] = 1e-300
+        out, gains, _ = ops.loudness_normalise(rows[B:], v, target_lufs=0.0, true_peak_db=0.0)
+    return [out[i, :r.numel()] for i, r in enumerate(rows[B:])], gains
 
 
 # ---- mel-cepstral distortion (include/swc_mcd.h) ----

@@ -989,6 +989,96 @@ def dtw(xf, yf, tx, ty, D=None, band=0, mode="warp", want=("total", "info", "mea
     return res
 
 
+LOUDNESS_VALUES = ("integrated", "range", "momentary_max", "short_term_max", "sample_peak", "true_peak", "blocks", "blocks_kept")
+
+
+def loudness_check_rate(sample_rate):
+    """fs of a swc_loudness call: a multiple of 10 in 8000 .. 48000 (include/swc_loudness.h), SwcError otherwise"""
+    try:
+        fs = int(sample_rate)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"loudness: sample_rate={sample_rate!r}")
+    if fs != sample_rate or not _lib.LOUDNESS_MIN_FS <= fs <= _lib.LOUDNESS_MAX_FS or fs % 10:
+        raise _lib.SwcError(f"loudness: sample_rate={sample_rate!r}: a multiple of 10 in {_lib.LOUDNESS_MIN_FS}..{_lib.LOUDNESS_MAX_FS} "
+                            "(include/swc_loudness.h)")
+    return fs
+
+
+def loudness_coefficients(sample_rate):
+    """swc_loudness_coefficients of include/swc_loudness.h: the K-weighting of the rate as ten float64 numbers, shelf b0 b1 b2 a1
+    a2 then high-pass b0 b1 b2 a1 a2 (host arithmetic, no GPU)"""
+    fs = loudness_check_rate(sample_rate)
+    k = (C.c_double * 10)()
+    if _lib.load().swc_loudness_coefficients(fs, k) != 0:
+        raise _lib.SwcError(f"loudness: no coefficients for sample_rate={fs}")
+    return list(k)
+
+
+def loudness_workspace_bytes(B, max_n_in, sample_rate):
+    """swc_loudness_workspace_bytes of include/swc_loudness.h"""
+    v = int(_lib.load().swc_loudness_workspace_bytes(int(B), int(max_n_in), int(sample_rate)))
+    if v < 0:
+        raise _lib.SwcError(f"loudness: no workspace size for B={B}, max_n_in={max_n_in}, sample_rate={sample_rate}")
+    return v
+
+
+def loudness(x_rows, sample_rate, max_n_in=None, out=None, workspace=None):
+    """The eight loudness values of every row of a ragged batch in one call (include/swc_loudness.h swc_loudness): x_rows = a list
+    of 1-D f32 device tensors at sample_rate -> float64 [B][8] in the order of LOUDNESS_VALUES: integrated loudness (LUFS),
+    loudness range (LU), the largest momentary and short-term loudness, sample peak and true peak (linear), the momentary
+    blocks and those kept by both gates; NaN where a value is not defined.  The true peak uses the table of
+    resample_table(1, 4).  max_n_in, out, workspace (tests): the host's length bound, a dict {"values": tensor} to write and
+    a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    fs = loudness_check_rate(sample_rate)
+    n_in, _, device = _pair_rows("loudness", x_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_in)
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    if not 0 <= max_n <= _lib.LOUDNESS_MAX_N:
+        raise _lib.SwcError(f"loudness: a row of {max_n} samples: at most {_lib.LOUDNESS_MAX_N} (include/swc_loudness.h)")
+    t = resample_table(1, 4, device)
+    workspace = _workspace("loudness", loudness_workspace_bytes(B, max_n, fs), workspace, device)
+    res = _outputs("loudness", {"values": ((B, _lib.LOUDNESS_VALUES), torch.float64)}, out, device, torch.empty)
+    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
+    _lib.check(lib.swc_loudness(_ptr(xp), _ptr(n), max_n, fs, t["width"], _ptr(t["taps"]), _ptr(t["start"]), t["run"],
+                                _ptr(res["values"]), _ptr(workspace), workspace.numel(), B, _stream()), "swc_loudness")
+    return res["values"]
+
+
+def loudness_normalise(x_rows, values, target_lufs=-23.0, true_peak_db=-1.0, cols=None, out=None):
+    """Rows scaled to target_lufs under a true-peak ceiling of true_peak_db, from `values` = loudness(x_rows, ...) as it stands on
+    the device: nothing is read back (include/swc_loudness.h swc_loudness_normalise).  -> (out f32 [B][cols]: row b holds its
+    scaled samples and zeros behind them, gains f32 [B], flags int32 [B]: bit 0 = not measured (the gain is 1), bit 1 = the
+    ceiling set the gain).  cols defaults to the longest row; a longer row is cut.  `out` (tests): an f32 device view [B, cols]
+    with unit column stride to write into instead."""
+    lib = _lib.load()
+    n_in, _, device = _pair_rows("loudness_normalise", x_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_in)
+    try:
+        target, ceiling = float(target_lufs), float(true_peak_db)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"loudness_normalise: target_lufs={target_lufs!r}, true_peak_db={true_peak_db!r}")
+    if not (abs(target) <= 1e3 and abs(ceiling) <= 1e3):
+        raise _lib.SwcError(f"loudness_normalise: target_lufs={target_lufs!r}, true_peak_db={true_peak_db!r}: finite numbers")
+    _chk(values, "loudness_normalise values", torch.float64)
+    if values.numel() != B * _lib.LOUDNESS_VALUES or not values.is_contiguous():
+        raise _lib.SwcError(f"loudness_normalise: values is a contiguous tensor of {B} x {_lib.LOUDNESS_VALUES} elements")
+    if out is None:
+        cols = max(n_in) if cols is None else int(cols)
+        out = torch.empty((B, cols), device=device, dtype=torch.float32)
+    else:
+        _chk(out, "loudness_normalise out", torch.float32)
+        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
+            raise _lib.SwcError("loudness_normalise: out must be [B, cols] with unit column stride")
+        cols = out.shape[1]
+    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
+    res = _outputs("loudness_normalise", {"gains": ((B,), torch.float32), "flags": ((B,), torch.int32)}, None, device, torch.empty)
+    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
+    _lib.check(lib.swc_loudness_normalise(_ptr(xp), _ptr(n), _ptr(values), target, ceiling, _ptr(out), ld, cols, _ptr(res["gains"]),
+                                          _ptr(res["flags"]), B, _stream()), "swc_loudness_normalise")
+    return out, res["gains"], res["flags"]
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""

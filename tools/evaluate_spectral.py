@@ -8,6 +8,9 @@ pairs (the distances are not defined: NaN) are listed by name and left out of th
 
 --align {none,waveform,envelope} [--max_lag_ms 50] finds every pair's constant delay first and scores the aligned views; the
 summary then adds the mean and the largest |lag| and the pairs whose correlation is <= 0 or not defined (tools/evaluate_stoi.py).
+
+--level_match brings every reconstruction to its original's integrated loudness first (metrics.spectral(level="loudness"),
+BS.1770-4 on the GPU) and prints the mean gain in dB: a codec that is 1 dB hot is then not charged for it in the distances.
 """
 import argparse
 import math
@@ -30,6 +33,8 @@ def build_parser():
     p.add_argument("--sample_rate", type=int, default=16000, help="rate the pairs are scored at (any: it sets the mel banks)")
     p.add_argument("--batch_size", type=int, default=32, help="pairs per swc_spectral call")
     p.add_argument("--verbose", action="store_true", help="print every file's values")
+    p.add_argument("--level_match", action="store_true",
+                   help="scale every reconstruction to its original's integrated loudness before scoring, and report the gain")
     add_align_arguments(p)
     return p
 
@@ -51,8 +56,8 @@ def main(argv=None):
     from simwhisper_codec_amd import metrics
 
     def score(ref, deg, dev):
-        q = metrics.spectral(ref, deg, sample_rate=args.sample_rate, device=dev)
-        return {k: q[k] for k in ("mel", "stft", "lsd")}
+        q = metrics.spectral(ref, deg, sample_rate=args.sample_rate, device=dev, level="loudness" if args.level_match else None)
+        return {k: q[k] for k in ("mel", "stft", "lsd") + (("gain_db",) if args.level_match else ())}
     names, cols, _, _ = score_batches(args, score)
     if args.verbose:
         for n, a, b, c in zip(names, cols["mel"], cols["stft"], cols["lsd"]):
@@ -67,6 +72,9 @@ def main(argv=None):
     print(f"mean mel distance: {m['mel']:.4f} over {scored} pairs")
     print(f"mean STFT distance: {m['stft']:.4f} over {scored} pairs")
     print(f"mean LSD: {m['lsd']:.4f} over {scored} pairs")
+    if args.level_match:
+        g = [v for v in cols["gain_db"] if not math.isnan(v)]
+        print(f"mean level-match gain: {_mean(g):+.2f} dB over {len(g)} pairs" if g else "mean level-match gain: no pair measured")
     return 0
 
 
