@@ -83,6 +83,14 @@ int swc_delay_us(int32_t us, void* stream);
  * state the library holds besides the error text) and applies to every later call of that thread until replaced;
  * NULL (the default) turns the accounting off.  The caller zeroes and reads the array; a non-zero count after
  * an encode means the codes may differ from the reference's and the stage must be re-run on exact-f32 operands.
+ * Producers: swc_layernorm, swc_snake_aa, swc_cast_f32_f16s, swc_cast_fp8, swc_gemm (split-f16 and fp8 outputs, every
+ * geometry), swc_proj_ln (y_next) and swc_layer_tail (the fp8 LayerNorm output of fc1_dtype = SWC_FP8); tests/sat_sites.py
+ * lists every site.  Only values the call stores count: rows >= M, rows >= lens[b] and rows in [t_in, t_out) never do.
+ * The count is CONSERVATIVE: a thread counts when the largest |scaled value| it converted EXCEEDS the largest finite number of
+ * the format (65504, 448) — scaled values between that number and the next rounding boundary (65520, 464) count although
+ * round-to-nearest would have brought them into range; a value equal to the limit does not count.  +-Inf counts and is stored
+ * as the finite limit.  Not counted, by construction in range: the split-f16 output of swc_attention16 (a convex combination of
+ * in-range v), swc_istft_spec (|S| <= 100), zero rows.  Not counted although it CAN clip: swc_attention_ex, see there.
  */
 int swc_set_saturation_counter(uint32_t* counters);
 
@@ -174,7 +182,11 @@ int swc_attention(const void* qkv, void* out, const int32_t* lens, int32_t B, in
  */
 int swc_attention16(const void* qkv, void* out, const int32_t* lens, int32_t B, int32_t T, int32_t H,
                     int32_t dtype, const int32_t* row_start, void* stream);
-/* f32 qkv in and the output written as out_dtype (F32 | F16S at SWC_F16S_ACT_SCALE), exact-f32 MFMA */
+/* f32 qkv in and the output written as out_dtype (F32 | F16S at SWC_F16S_ACT_SCALE), exact-f32 MFMA.
+ * The F16S form SATURATES UNCOUNTED: its f32 v is not bounded, so the weighted sums can leave |x| <= 1023.5; they are stored as
+ * the finite limit +-65504 / 64 and swc_set_saturation_counter's counters do not move.  A caller that needs the guard checks the
+ * range of v itself (max |out| <= max |v|).  AudioCodec never takes this form: its split-f16 preset writes q/k/v as split-f16
+ * from the GEMM epilogue (counted there) and runs swc_attention16, whose output is then in range by construction. */
 int swc_attention_ex(const void* qkv, void* out, const int32_t* lens, int32_t B, int32_t T, int32_t H,
                      int32_t out_dtype, void* stream);
 

@@ -18,6 +18,7 @@ Work the reference does and this path provably does not need:
 Ragged `decode` batches are padded to the batch maximum exactly like the reference,
 because its un-masked up-sampler / Vocos make short utterances depend on that maximum.
 """
+import contextlib
 import functools
 import logging
 import math
@@ -278,31 +279,107 @@ class AudioCodec(nn.Module):
         if st is None or st["dev"] != dev:
             # (not inference tensors, whatever the caller's mode: saturation_count() updates the host copy in place later)
             with torch.inference_mode(False):
-                st = {"dev": dev, "buf": torch.zeros(2, dtype=torch.int32, device=dev),
-                      "host": torch.zeros(2, dtype=torch.int32).pin_memory(),
-                      "snap": torch.zeros(2, dtype=torch.int32).pin_memory(), "snap_ev": None,
-                      "seen": [0, 0], "warned": False}
+                # one device array of four counters: the encode side's pair {split-f16, fp8} and the decode side's own pair behind
+                # it (_decode_counters), so that every read-back and every snapshot of the one brings the other along for free
+                both = torch.zeros(4, dtype=torch.int32, device=dev)
+                st = {"dev": dev, "all": both, "buf": both[:2], "dbuf": both[2:],
+                      "host": torch.zeros(4, dtype=torch.int32).pin_memory(),
+                      "snap": torch.zeros(4, dtype=torch.int32).pin_memory(), "snap_ev": None,
+                      "seen": [0, 0], "warned": False,
+                      "dseen": [0, 0], "dwarned": False, "dpending": False}
             self.__dict__["_sat"] = st
         return st
 
-    def saturation_count(self):
-        """{"f16s": n, "fp8": n}: producer threads that clipped a split-f16 / fp8 activation since the model was moved
-        to its device (include/swc.h swc_set_saturation_counter).  Synchronises the stream."""
+    def saturation_count(self, side="encode"):
+        """{"f16s": n, "fp8": n}: producer threads that clipped a split-f16 / fp8 activation since the model was moved to its
+        device (include/swc.h swc_set_saturation_counter).  side="encode" (default): the encode side's pair, the one the range
+        guard acts on; side="decode": the pair of the decode side (up-sampler, decoder transformer, Vocos), counted apart;
+        side="all": both, as {"f16s", "fp8", "decode_f16s", "decode_fp8"}.  Synchronises the stream."""
+        if side not in ("encode", "decode", "all"):
+            raise SwcError(f"saturation_count: side={side!r}: expected 'encode', 'decode' or 'all'")
         st = self.__dict__.get("_sat")
-        if st is None:
-            return {"f16s": 0, "fp8": 0}
-        with torch.cuda.device(st["dev"]):
-            st["host"].copy_(st["buf"], non_blocking=True)
+        n = [0, 0, 0, 0]
+        if st is not None:
+            with torch.cuda.device(st["dev"]):
+                st["host"].copy_(st["all"], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+            n = [int(v) for v in st["host"].tolist()]
+            self._report_decode_clips(st, n[2:])
+        if side == "encode":
+            return {"f16s": n[0], "fp8": n[1]}
+        if side == "decode":
+            return {"f16s": n[2], "fp8": n[3]}
+        return {"f16s": n[0], "fp8": n[1], "decode_f16s": n[2], "decode_fp8": n[3]}
+
+    # ---- decode side.  Its reduced-range producers (Vocos' final LayerNorm writes split-f16 in every 16-bit preset; the
+    # split-f16 / fp8 decode presets have more) count into a pair of their own: there is no exact-f32 re-run of a decode, and
+    # a clip there says nothing about the codes of an encode.  Policy vocabulary as on the encode side: "fallback" warns
+    # once (nothing to fall back to), "raise" raises from the decode call itself (one read-back and stream synchronisation
+    # per decode), "ignore" counts only, "off" does not read the counters.
+    @contextlib.contextmanager
+    def _decode_counters(self):
+        """the decode part of an entry point runs with the decode side's counter pair installed; the pair that was in force
+        (the encode side's, installed by _on_model_device) is back afterwards, also around the decode of forward()"""
+        st = self._sat_state(self._buffers_device())
+        prev = getattr(_TLS, "counter", None)
+        ops.set_saturation_counter(st["dbuf"])
+        _TLS.counter = st["dbuf"]
+        try:
+            yield
+        finally:
+            ops.set_saturation_counter(prev)
+            _TLS.counter = prev
+
+    def _report_decode_clips(self, st, n, may_raise=False):
+        """n: the decode side's pair as just read (a full read-back, or a snapshot: older values report nothing)"""
+        st["dpending"] = False
+        new = [max(0, int(n[i]) - st["dseen"][i]) for i in (0, 1)]
+        st["dseen"] = [max(st["dseen"][i], int(n[i])) for i in (0, 1)]
+        if not any(new) or self.saturation_policy in ("off", "ignore"):
+            return
+        if self.saturation_policy == "raise" and may_raise:
+            raise SwcError(f"decode-side reduced-range operands clipped ({new[0]} split-f16 and {new[1]} fp8 producer threads "
+                           "saw an activation beyond the format's range): the waveform of this call is not reliable; use "
+                           "precision='fp32'")
+        if not st["dwarned"]:
+            st["dwarned"] = True
+            logging.warning("decode-side reduced-range operands clipped (%d split-f16 producer threads saw |activation| >= 1023, "
+                            "%d fp8 ones |activation| >= 28): decode has no exact-f32 re-run, the waveform may differ from the "
+                            "reference's beyond the preset's tolerance; saturation_count() keeps counting", new[0], new[1])
+
+    def _after_decode(self):
+        """Behind the decode kernels of one call.  "raise" reads the counters back now.  Otherwise nothing is enqueued and nothing
+        waits: the decode side's pair travels with the next read-back or snapshot of the encode side (every encode of an
+        encode -> decode round trip takes one) and is reported there.  Only a decode that follows a decode nobody has looked at
+        since (decode-only use) leaves a snapshot of its own behind, which the next decode looks at once its event has completed."""
+        if self.saturation_policy == "off" or torch.cuda.is_current_stream_capturing():  # (a captured decode: the counts stay
+            return                                                                       # readable with saturation_count())
+        st = self._sat_state(self._buffers_device())
+        if self.saturation_policy == "raise":
+            st["host"].copy_(st["all"], non_blocking=True)
             torch.cuda.current_stream().synchronize()
-        n = st["host"].tolist()
-        return {"f16s": int(n[0]), "fp8": int(n[1])}
+            self._report_decode_clips(st, st["host"].tolist()[2:], may_raise=True)
+            return
+        if not st["dpending"]:
+            st["dpending"] = True
+            return
+        if st["snap_ev"] is not None:
+            if not st["snap_ev"].query():
+                return                       # the last snapshot is still in flight: it is looked at by a later call
+            if self.__dict__.get("_defer", 0) > 0:
+                return                       # ... and inside a deferred block the check at its end owns it
+            # only the decode side's pair is looked at here; the encode side's arithmetic stays with the encode-side callers (the
+            # counters are cumulative: the snapshot taken below holds whatever this one held for them)
+            self._report_decode_clips(st, st["snap"].tolist()[2:])
+        self._snapshot_counters()
+        st["dpending"] = True
 
     def _snapshot_counters(self):
         """enqueue a copy of the clip counters into pinned memory behind the kernels enqueued so far, with an event: the
         deferred check later waits for THAT point of the stream only, not for what was enqueued after it"""
         st = self._sat_state(self._buffers_device())
         with torch.cuda.device(st["dev"]), torch.inference_mode(False):
-            st["snap"].copy_(st["buf"], non_blocking=True)
+            st["snap"].copy_(st["all"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         st["snap_ev"] = ev
@@ -347,10 +424,14 @@ class AudioCodec(nn.Module):
             st["snap_ev"].synchronize()
             v = st["snap"].tolist()
             n, st["snap_ev"] = {"f16s": int(v[0]), "fp8": int(v[1])}, None
+            self._report_decode_clips(st, v[2:])
         else:
             n = self.saturation_count()
-        new16, new8 = n["f16s"] - st["seen"][0], n["fp8"] - st["seen"][1]
-        st["seen"] = [n["f16s"], n["fp8"]]
+            st["snap_ev"] = None  # a pending snapshot is older than this read-back: it has nothing left to report
+        # the counters only grow, but a snapshot can be older than `seen` (a full read-back was checked after it was taken):
+        # such a snapshot reports nothing and must not move `seen` back
+        new16, new8 = max(0, n["f16s"] - st["seen"][0]), max(0, n["fp8"] - st["seen"][1])
+        st["seen"] = [max(st["seen"][0], n["f16s"]), max(st["seen"][1], n["fp8"])]
         if new8 and not st["warned"]:
             st["warned"] = True
             logging.warning("fp8 preset: %d producer threads clipped activations at |x| = 28 in this call "
@@ -991,6 +1072,12 @@ class AudioCodec(nn.Module):
         of their 3000 frames: the local-receptive-field vocoder then runs on 2000 + halo frames).
         ragged (decode() only): samples beyond a row's own length lat_i * 1280 are never looked at, so the ConvNeXt
         blocks skip the 128-frame tiles that lie beyond lat_i * 8 + VOCOS_HALO_FRAMES frames of row i."""
+        with self._decode_counters():
+            wav = self._decode_latent_impl(zq, lat_host, B, T, P, keep_frames, ragged)
+        self._after_decode()
+        return wav
+
+    def _decode_latent_impl(self, zq, lat_host, B, T, P, keep_frames, ragged):
         Tt = P.stack * T
         x = self._upsample(zq, B, T, P)
         mel = self._decoder(x, lat_host, B, Tt, P)

@@ -380,6 +380,9 @@ __global__ __launch_bounds__(256, 1) void mlp_block_kernel(const float* x, float
                     if constexpr (F8) {
                         // e4m3 at the activation scale, B fragments of the 16 x 16 x 128 MFMA: fragment (s = c / 128, tb = token / 16)
                         // = 2 KiB as two lane-linear halves; lane' = 16 ((c % 128) / 32) + token % 16 holds 32 channels
+                        // (tokens beyond M run on x = 0 and a copy of the last row's attention and are never stored: what they
+                        // convert is not an activation of the call and must not reach the clip counter)
+                        float am = 0.f;
 #pragma unroll
                         for (int hq = 0; hq < 2; ++hq) {
                             const int c = 192 * w + 32 * n + 8 * (2 * t + hq) + 4 * lh;
@@ -388,8 +391,9 @@ __global__ __launch_bounds__(256, 1) void mlp_block_kernel(const float* x, float
                                             (16 * ((c & 127) >> 5) + (tok & 15)) * 16 + (c & 15);
                             *reinterpret_cast<unsigned*>(smem + off) =
                                 fp8_pack4(o[4 * hq] * SWC_FP8_ACT_SCALE, o[4 * hq + 1] * SWC_FP8_ACT_SCALE, o[4 * hq + 2] * SWC_FP8_ACT_SCALE,
-                                          o[4 * hq + 3] * SWC_FP8_ACT_SCALE, amax8);
+                                          o[4 * hq + 3] * SWC_FP8_ACT_SCALE, am);
                         }
+                        if (row0 + 32 * fb + lf < M) amax8 = fmaxf(amax8, am);
                     } else {
                         if constexpr (F16)
                             *reinterpret_cast<u32x4*>(smem + (2 * (12 * w + 2 * n + t) + fb) * ML_YP + lane * 16) =
