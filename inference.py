@@ -104,6 +104,17 @@ def build_parser():
     p.add_argument("--true_peak_db", type=float, default=-1.0, metavar="DB",
                    help="with --loudness: the true-peak ceiling in dB relative to full scale; the gain is lowered where the "
                         "target loudness would exceed it")
+    p.add_argument("--active_level", type=float, default=None, metavar="DBOV",
+                   help="active speech level to normalise to (ITU-T P.56; -26 dBov before P.862 / P.863 / P.808 tests), on the "
+                        "GPU and single-GPU only.  Default: off, every file is written as before.  --mode roundtrip / encode: "
+                        "every input is brought to that active level before it is encoded, with a gain of at most 1 / peak "
+                        "(AudioCodec.encode(active_level=), metrics.level_normalised); a file with no measurable speech "
+                        "passes unchanged.  Not together with --loudness")
+    p.add_argument("--trim_silence", action="store_true",
+                   help="--mode roundtrip / encode, on the GPU and single-GPU only: leading and trailing silence is cut from "
+                        "every input before it is encoded (metrics.trimmed: the P.56 activity criterion), so the output has "
+                        "the trimmed length; the offsets are logged.  A file in which no speech is found passes untrimmed.  "
+                        "Default: off")
     return p
 
 
@@ -197,9 +208,17 @@ def main(argv=None):
                          f"(WORLD_SIZE={world}); data-parallel runs write WAV")
     if world > 1 and args.loudness is not None:
         raise SystemExit(f"--loudness normalises on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
+    if args.active_level is not None and args.loudness is not None:
+        raise SystemExit("--active_level and --loudness are two ways to set one level: give one of them")
+    if world > 1 and (args.active_level is not None or args.trim_silence):
+        raise SystemExit(f"--active_level / --trim_silence run on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    if (args.active_level is not None or args.trim_silence) and device.type != "cuda":
+        raise SystemExit("--active_level / --trim_silence find the speech on the GPU: --device must be a CUDA device")
+    if (args.active_level is not None or args.trim_silence) and args.mode == "decode":
+        raise SystemExit("--active_level / --trim_silence act on the input of --mode roundtrip / encode; --mode decode reads codes")
     if args.loudness is not None and device.type != "cuda":
         raise SystemExit("--loudness measures and normalises on the GPU: --device must be a CUDA device")
     flac_out = args.output_format == "flac"
@@ -227,6 +246,8 @@ def main(argv=None):
 
     on_gpu = device.type == "cuda"
     level = {} if args.loudness is None else {"loudness": args.loudness, "true_peak_db": args.true_peak_db}
+    if args.active_level is not None:
+        level = {"active_level": args.active_level}
 
     def load_one(path):
         return load_file(path, generator.input_sample_rate, on_gpu, args.resample, args.flac)
@@ -289,6 +310,15 @@ def main(argv=None):
         paths, wav_list = item
         with torch.no_grad():
             t1 = time.perf_counter()
+            if args.trim_silence:
+                from simwhisper_codec_amd import metrics
+                cut, bounds = metrics.trimmed(wav_list, generator.input_sample_rate, device=device)
+                for k, (path, (a, b)) in enumerate(zip(paths, bounds)):
+                    if b > a:
+                        logging.info(f"{path}: trimmed to samples [{a}, {b}) of {len(wav_list[k])}")
+                    else:
+                        logging.info(f"{path}: no speech found, left untrimmed")
+                wav_list = [c if b > a else w for c, w, (a, b) in zip(cut, wav_list, bounds)]
             def round_trip():
                 codes = model.encode(wav_list, overlap_seconds=10, device=device, **level)["codes_list"]
                 if to_codes:   # the file images of the batch, packed on the device by one launch (inside the range check)

@@ -238,6 +238,22 @@ LOUDNESS_SIGNATURES = {
     "swc_loudness_normalise": ([_P, _P, _P, _D, _D, _P, _L, _L, _P, _P, _I, _P], C.c_int),
 }
 
+# include/swc_activity.h (P.56 active speech level, the runs of active samples, the device-side level gain), one to one.  The
+# twelfth table of its own
+ACTIVITY_MIN_FS, ACTIVITY_MAX_FS = 8000, 48000   # SWC_ACTIVITY_MIN_FS / _MAX_FS
+ACTIVITY_MAX_N = 1 << 30                         # SWC_ACTIVITY_MAX_N
+ACTIVITY_MAX_HANGOVER = 24000                    # SWC_ACTIVITY_MAX_HANGOVER
+ACTIVITY_SUBBLOCK, ACTIVITY_GROUP = 256, 64      # SWC_ACTIVITY_SUBBLOCK / _GROUP
+ACTIVITY_TILE, ACTIVITY_THREADS = 4096, 256      # SWC_ACTIVITY_TILE / _THREADS
+ACTIVITY_THRESHOLDS, ACTIVITY_VALUES = 15, 8     # SWC_ACTIVITY_THRESHOLDS / _VALUES
+ACTIVITY_UNMEASURED, ACTIVITY_PEAK_LIMITED = 1, 2   # SWC_ACTIVITY_UNMEASURED / _PEAK_LIMITED
+ACTIVITY_SIGNATURES = {
+    "swc_activity_coefficients": ([_I, _D, C.POINTER(_D), C.POINTER(_I), C.POINTER(_I), C.POINTER(_D)], C.c_int),
+    "swc_activity_workspace_bytes": ([_I, _L, _I], C.c_int64),
+    "swc_activity": ([_P, _P, _L, _I, _D, _D, _P, _P, _P, _L, _P, _L, _I, _P], C.c_int),
+    "swc_activity_normalise": ([_P, _P, _P, _D, _P, _L, _L, _P, _P, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -258,7 +274,7 @@ def load():
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
-                  LOUDNESS_SIGNATURES):
+                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

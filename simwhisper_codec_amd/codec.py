@@ -1321,7 +1321,8 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
-    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, loudness=None, true_peak_db=-1.0):
+    def encode(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, loudness=None, true_peak_db=-1.0,
+               active_level=None):
         """model.py:244-308: 30 s windows every (30 - overlap) s, keep the first 250 codes of each window,
         concatenate, trim to len // 1280.  Returns {"codes_list": [IntTensor(G, T_i)]}.
         sample_rate: None = the waveforms are at input_sample_rate (the reference's contract).  An int, or one int per
@@ -1329,7 +1330,12 @@ class AudioCodec(nn.Module):
         then windowed as usual), so row i yields ceil(input_sample_rate n_i / sr_i) // 1280 code frames.
         loudness: None = the rows as given.  A number: every row is first brought to that integrated loudness (LUFS, EBU R128:
         -23) under a true-peak ceiling of true_peak_db, at input_sample_rate and on the GPU (metrics.normalised: the gain is
-        computed and applied on the device, nothing is read back, so it composes with deferred_range_check())."""
+        computed and applied on the device, nothing is read back, so it composes with deferred_range_check()).
+        active_level: None = the rows as given.  A number: every row is first brought to that ITU-T P.56 active speech level
+        (dBov: -26) with a gain of at most 1 / peak, in the same way (metrics.level_normalised).  Not together with
+        loudness=: a row has one level."""
+        if loudness is not None and active_level is not None:
+            raise SwcError("encode: loudness= and active_level= are two ways to set one level: give one of them")
         B = len(wav_list)
         if B == 0:
             return {"codes_list": []}
@@ -1341,6 +1347,12 @@ class AudioCodec(nn.Module):
             if dev.type != "cuda":
                 raise SwcError("encode(loudness=): the meter is a HIP kernel (there is no CPU fallback)")
             wav_list = metrics.normalised(wav_list, self.input_sample_rate, target_lufs=loudness, true_peak_db=true_peak_db, device=dev)[0]
+        if active_level is not None:
+            from . import metrics
+            dev = self._resolve_device(device)
+            if dev.type != "cuda":
+                raise SwcError("encode(active_level=): the activity detector is a HIP kernel (there is no CPU fallback)")
+            wav_list = metrics.level_normalised(wav_list, self.input_sample_rate, target_dbov=active_level, device=dev)[0]
         n = [int(w.shape[-1]) if w.dim() else 0 for w in wav_list]
         dev = self._resolve_device(device)
         # Rows are independent, so the batch is assembled longest utterance first: workgroups are dispatched row by row
@@ -1596,6 +1608,28 @@ class AudioCodec(nn.Module):
         deg = metrics.loudness(syn, sample_rate=self.input_sample_rate, device=dev)
         res = {"ref": ref, "deg": deg}
         for k in ("integrated", "range", "true_peak_db"):
+            res[k + "_diff"] = deg[k] - ref[k]
+        return res
+
+    @_on_model_device
+    @torch.inference_mode()
+    def active_level(self, wav_list, overlap_seconds=10, device=torch.device("cuda")):
+        """quality() for the speech levels: encode -> decode -> metrics.active_level of the input and of the reconstruction (at
+        input_sample_rate).  -> dict on the model's device: "ref" and "deg", each the dict of metrics.active_level, and
+        "active_level_db_diff", "long_term_db_diff", "activity_diff" (deg - ref, float64 [B]; NaN where either side is)."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("active_level: the activity detector is a HIP kernel (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        ref = metrics.active_level(wav_list, sample_rate=self.input_sample_rate, device=dev)
+        deg = metrics.active_level(syn, sample_rate=self.input_sample_rate, device=dev)
+        res = {"ref": ref, "deg": deg}
+        for k in ("active_level_db", "long_term_db", "activity"):
             res[k + "_diff"] = deg[k] - ref[k]
         return res
 

@@ -550,6 +550,138 @@ def level_matched(ref_list, deg_list, sample_rate, device=torch.device("cuda")):
     return [out[i, :r.numel()] for i, r in enumerate(rows[B:])], gains
 
 
+# ---- speech activity (include/swc_activity.h) ----
+
+ACTIVE_LEVEL_KEYS = ("active_level_db", "long_term_db", "activity", "threshold_db", "sample_peak_db")
+
+
+def _activity_device(who, sample_rate, device):
+    ops.activity_check_rate(sample_rate)
+    device = _cuda(who, "the activity detector is a HIP kernel", device)
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def active_level(wav_list, sample_rate=16000, margin_db=15.9, hangover_ms=200, device=torch.device("cuda")):
+    """The ITU-T P.56 active speech level of every waveform of a list, in one swc_activity call (include/swc_activity.h): 1-D
+    mono waveforms at sample_rate (an integer in 8000 .. 48000; host or device tensors).  -> dict on `device`, a float64 tensor
+    [B] per key: "active_level_db" (the power over the time the talker is active, dB relative to full scale), "long_term_db"
+    (the power over the whole row), "activity" (the fraction of the row that is active), "threshold_db" (the envelope level
+    above which a sample counts as active: margin_db under the active level) and "sample_peak_db".  NaN where a value is not
+    defined (an empty or silent row, or one whose envelope never comes within margin_db of its level).  Nothing is
+    synchronised."""
+    device = _activity_device("active_level", sample_rate, device)
+    if len(wav_list) == 0:
+        return {k: torch.zeros(0, device=device, dtype=torch.float64) for k in ACTIVE_LEVEL_KEYS}
+    with torch.cuda.device(device):
+        v = ops.activity(_rows(wav_list, device), sample_rate, margin_db, hangover_ms / 1000.0)["values"]
+        return {"active_level_db": v[:, 0], "long_term_db": v[:, 1], "activity": v[:, 2], "threshold_db": 20.0 * torch.log10(v[:, 3]),
+                "sample_peak_db": 20.0 * torch.log10(v[:, 4])}
+
+
+def _ms(ms, sample_rate):
+    return int(math.floor(ms * sample_rate / 1000.0 + 0.5))
+
+
+def segment_policy(run_list, sample_rate, hangover_ms=200, min_speech_ms=50, pre_ms=60):
+    """The host policy on one row's run list [(start, end)] (plain integers, no GPU): a run whose length without its hangover
+    is under min_speech_ms is dropped; every start moves back by pre_ms (the envelope lags the onset), clamped at 0; runs that
+    then touch or overlap are merged.  -> [(start, end)]"""
+    hang = ops.activity_coefficients(sample_rate, hangover_ms / 1000.0)["hangover"]
+    keep, pre = _ms(min_speech_ms, sample_rate), _ms(pre_ms, sample_rate)
+    out = []
+    for s, e in run_list:
+        if e - s - hang < keep:
+            continue
+        s = max(0, s - pre)
+        if out and s <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], e))
+        else:
+            out.append((s, e))
+    return out
+
+
+def split_policy(segs, max_len):
+    """The pieces, none longer than max_len samples where a pause allows it, of the span of one row's segments [(start, end)]
+    (plain integers, no GPU).  A piece longer than max_len is cut at its longest interior pause; ties go to the pause whose
+    midpoint is nearest the piece's midpoint, then to the earlier one; the left piece ends at the pause's start and the right
+    piece begins at its end; both are cut again.  A piece with no pause is cut into ceil(len / max_len) parts at
+    start + floor(k len / parts).  -> [(start, end)]"""
+    if not segs:
+        return []
+    s, e = segs[0][0], segs[-1][1]
+    if e - s <= max_len:
+        return [(s, e)]
+    if len(segs) == 1:
+        parts = -(-(e - s) // max_len)
+        return [(s + k * (e - s) // parts, s + (k + 1) * (e - s) // parts) for k in range(parts)]
+    k = min(range(len(segs) - 1), key=lambda i: (segs[i][1] - segs[i + 1][0], abs(segs[i][1] + segs[i + 1][0] - (s + e)), i))
+    return split_policy(segs[:k + 1], max_len) + split_policy(segs[k + 1:], max_len)
+
+
+def _segments(who, wav_list, sample_rate, margin_db, hangover_ms, min_speech_ms, pre_ms, device):
+    """-> (the staged rows, per row the segments after the policy): one swc_activity call, one small read-back (the run counts
+    and the run lists together)"""
+    device = _activity_device(who, sample_rate, device)
+    if len(wav_list) == 0:
+        return [], []
+    with torch.cuda.device(device):
+        rows = _rows(wav_list, device)
+        res = ops.activity(rows, sample_rate, margin_db, hangover_ms / 1000.0)
+        B, cap = res["runs"].shape[:2]
+        back = torch.cat([res["values"][:, 6].to(torch.int64), res["runs"].reshape(-1)]).cpu().tolist()
+    segs = []
+    for b in range(B):
+        at = B + b * cap * 2
+        run_list = [(back[at + 2 * r], back[at + 2 * r + 1]) for r in range(back[b])]
+        segs.append(segment_policy(run_list, sample_rate, hangover_ms, min_speech_ms, pre_ms))
+    return rows, segs
+
+
+def speech_segments(wav_list, sample_rate=16000, margin_db=15.9, hangover_ms=200, min_speech_ms=50, pre_ms=60, device=torch.device("cuda")):
+    """Where the speech is: per row, the list of (start, end) sample intervals that the P.56 activity criterion marks
+    (include/swc_activity.h: the envelope above a threshold margin_db under the active level, with hangover_ms of hangover),
+    after segment_policy().  The criterion is a deterministic, text-defined detector for clean speech: there is no model and no
+    noise-floor tracking.  One kernel call for the batch and one small read-back."""
+    return _segments("speech_segments", wav_list, sample_rate, margin_db, hangover_ms, min_speech_ms, pre_ms, device)[1]
+
+
+def trimmed(wav_list, sample_rate=16000, margin_db=15.9, hangover_ms=200, min_speech_ms=50, pre_ms=60, device=torch.device("cuda")):
+    """Every waveform without its leading and trailing silence: -> (rows, bounds): rows[i] = the view [first start, last end)
+    of row i as it stands on the device (zero-copy for a contiguous f32 device row; an empty view where no speech is found),
+    bounds[i] = (start, end)."""
+    rows, segs = _segments("trimmed", wav_list, sample_rate, margin_db, hangover_ms, min_speech_ms, pre_ms, device)
+    bounds = [(s[0][0], s[-1][1]) if s else (0, 0) for s in segs]
+    return [r[a:b] for r, (a, b) in zip(rows, bounds)], bounds
+
+
+def split_at_pauses(wav_list, sample_rate=16000, max_seconds=30.0, margin_db=15.9, hangover_ms=200, min_speech_ms=50, pre_ms=60,
+                    device=torch.device("cuda")):
+    """Every waveform trimmed and cut at its pauses into pieces of at most max_seconds where a pause allows it (split_policy()).
+    -> (pieces, index): pieces = zero-copy views of the rows, index[k] = (row, start, end) of piece k, in row order."""
+    rows, segs = _segments("split_at_pauses", wav_list, sample_rate, margin_db, hangover_ms, min_speech_ms, pre_ms, device)
+    max_len = int(math.floor(max_seconds * sample_rate + 0.5))
+    if max_len < 1:
+        raise SwcError(f"split_at_pauses: max_seconds={max_seconds!r}")
+    index = [(i, a, b) for i, s in enumerate(segs) for a, b in split_policy(s, max_len)]
+    return [rows[i][a:b] for i, a, b in index], index
+
+
+def level_normalised(wav_list, sample_rate, target_dbov=-26.0, margin_db=15.9, hangover_ms=200, device=torch.device("cuda")):
+    """Every waveform of a list brought to an active speech level of target_dbov (ITU-T P.56; -26 dBov is what P.862 / P.863 /
+    P.808 material is set to), with a gain of at most 1 / peak so that nothing clips: one swc_activity and one
+    swc_activity_normalise call, the gain computed on the device (no read-back, nothing synchronised).  -> (rows, gains,
+    flags): rows = views of ONE zero-padded batch, row i of its waveform's length; gains FloatTensor[B] (linear); flags
+    IntTensor[B], bit 0 = the row has no active level and is passed through with gain 1, bit 1 = the peak set the gain."""
+    device = _activity_device("level_normalised", sample_rate, device)
+    if len(wav_list) == 0:
+        return [], torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        rows = _rows(wav_list, device)
+        values = ops.activity(rows, sample_rate, margin_db, hangover_ms / 1000.0)["values"]
+        out, gains, flags = ops.activity_normalise(rows, values, target_dbov)
+    return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+
+
 # ---- mel-cepstral distortion (include/swc_mcd.h) ----
 
 MCD_MELS = 80

@@ -1079,6 +1079,112 @@ def loudness_normalise(x_rows, values, target_lufs=-23.0, true_peak_db=-1.0, col
     return out, res["gains"], res["flags"]
 
 
+ACTIVITY_VALUES = ("active_level", "long_term", "activity", "threshold", "sample_peak", "active_samples", "runs", "crossing")
+
+
+def activity_check_rate(sample_rate):
+    """fs of a swc_activity call: an integer in 8000 .. 48000 (include/swc_activity.h), SwcError otherwise"""
+    try:
+        fs = int(sample_rate)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"activity: sample_rate={sample_rate!r}")
+    if fs != sample_rate or not _lib.ACTIVITY_MIN_FS <= fs <= _lib.ACTIVITY_MAX_FS:
+        raise _lib.SwcError(f"activity: sample_rate={sample_rate!r}: an integer in {_lib.ACTIVITY_MIN_FS}..{_lib.ACTIVITY_MAX_FS} "
+                            "(include/swc_activity.h)")
+    return fs
+
+
+def activity_coefficients(sample_rate, hangover_s=0.2):
+    """swc_activity_coefficients of include/swc_activity.h (host arithmetic, no GPU) -> dict: "g" = exp(-1 / (0.03 fs)),
+    "hangover" = I in samples, "subblock" = the sub-block length, "transition" = the 2 x 2 state transition over one sub-block,
+    row-major"""
+    fs = activity_check_rate(sample_rate)
+    g, I, L, m = C.c_double(), C.c_int32(), C.c_int32(), (C.c_double * 4)()
+    if _lib.load().swc_activity_coefficients(fs, float(hangover_s), C.byref(g), C.byref(I), C.byref(L), m) != 0:
+        raise _lib.SwcError(f"activity: no coefficients for sample_rate={fs}, hangover_s={hangover_s!r} (at most "
+                            f"{_lib.ACTIVITY_MAX_HANGOVER} samples)")
+    return {"g": g.value, "hangover": I.value, "subblock": L.value, "transition": list(m)}
+
+
+def activity_workspace_bytes(B, max_n_in, sample_rate):
+    """swc_activity_workspace_bytes of include/swc_activity.h"""
+    v = int(_lib.load().swc_activity_workspace_bytes(int(B), int(max_n_in), int(sample_rate)))
+    if v < 0:
+        raise _lib.SwcError(f"activity: no workspace size for B={B}, max_n_in={max_n_in}, sample_rate={sample_rate}")
+    return v
+
+
+def activity_run_capacity(max_n_in, hangover):
+    """runs a row of at most max_n_in samples can have with a hangover of `hangover` samples: max_n_in // (I + 2) + 1"""
+    return int(max_n_in) // (int(hangover) + 2) + 1
+
+
+def activity(x_rows, sample_rate, margin_db=15.9, hangover_s=0.2, max_n_in=None, out=None, workspace=None):
+    """The P.56 active level and the runs of active samples of every row of a ragged batch in one call (include/swc_activity.h
+    swc_activity): x_rows = a list of 1-D f32 device tensors at sample_rate -> dict: "values" float64 [B][8] in the order of
+    ACTIVITY_VALUES (active level and long-term level in dB, activity factor, working threshold c* and sample peak (linear),
+    samples active at c*, runs, the crossing's threshold index; NaN where a value is not defined), "counts" int64 [B][15] (the
+    samples active at each threshold 2^(j - 15)), "runs" int64 [B][cap][2]: run r of row b as (start, end); entries from the
+    row's run count on are zero (or what a tensor of `out` held).  max_n_in, out, workspace (tests): the host's length bound,
+    a dict of tensors to write under the same names and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    fs = activity_check_rate(sample_rate)
+    n_in, _, device = _pair_rows("activity", x_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_in)
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    if not 0 <= max_n <= _lib.ACTIVITY_MAX_N:
+        raise _lib.SwcError(f"activity: a row of {max_n} samples: at most {_lib.ACTIVITY_MAX_N} (include/swc_activity.h)")
+    try:
+        margin, hang = float(margin_db), float(hangover_s)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"activity: margin_db={margin_db!r}, hangover_s={hangover_s!r}")
+    cap = activity_run_capacity(max_n, activity_coefficients(fs, hang)["hangover"])
+    workspace = _workspace("activity", activity_workspace_bytes(B, max_n, fs), workspace, device)
+    out = out or {}
+    res = _outputs("activity", {"values": ((B, _lib.ACTIVITY_VALUES), torch.float64), "counts": ((B, _lib.ACTIVITY_THRESHOLDS), torch.int64)},
+                   out, device, torch.empty)
+    res.update(_outputs("activity", {"runs": ((B, cap, 2), torch.int64)}, out, device, torch.zeros))   # beyond a row's count: not written
+    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
+    _lib.check(lib.swc_activity(_ptr(xp), _ptr(n), max_n, fs, margin, hang, _ptr(res["values"]), _ptr(res["counts"]), _ptr(res["runs"]),
+                                cap, _ptr(workspace), workspace.numel(), B, _stream()), "swc_activity")
+    res["runs"] = res["runs"].view(B, cap, 2)
+    return res
+
+
+def activity_normalise(x_rows, values, target_db=-26.0, cols=None, out=None):
+    """Rows scaled to an active level of target_db (dB relative to full scale) with a gain of at most 1 / peak, from `values` =
+    activity(x_rows, ...)["values"] as it stands on the device: nothing is read back (include/swc_activity.h
+    swc_activity_normalise).  -> (out f32 [B][cols]: row b holds its scaled samples and zeros behind them, gains f32 [B], flags
+    int32 [B]: bit 0 = not measured (the gain is 1), bit 1 = the peak set the gain).  cols defaults to the longest row; a
+    longer row is cut.  `out` (tests): an f32 device view [B, cols] with unit column stride to write into instead."""
+    lib = _lib.load()
+    n_in, _, device = _pair_rows("activity_normalise", x_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_in)
+    try:
+        target = float(target_db)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"activity_normalise: target_db={target_db!r}")
+    if not abs(target) <= 1e3:
+        raise _lib.SwcError(f"activity_normalise: target_db={target_db!r}: a finite number")
+    _chk(values, "activity_normalise values", torch.float64)
+    if values.numel() != B * _lib.ACTIVITY_VALUES or not values.is_contiguous():
+        raise _lib.SwcError(f"activity_normalise: values is a contiguous tensor of {B} x {_lib.ACTIVITY_VALUES} elements")
+    if out is None:
+        cols = max(n_in) if cols is None else int(cols)
+        out = torch.empty((B, cols), device=device, dtype=torch.float32)
+    else:
+        _chk(out, "activity_normalise out", torch.float32)
+        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
+            raise _lib.SwcError("activity_normalise: out must be [B, cols] with unit column stride")
+        cols = out.shape[1]
+    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
+    res = _outputs("activity_normalise", {"gains": ((B,), torch.float32), "flags": ((B,), torch.int32)}, None, device, torch.empty)
+    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
+    _lib.check(lib.swc_activity_normalise(_ptr(xp), _ptr(n), _ptr(values), target, _ptr(out), ld, cols, _ptr(res["gains"]),
+                                          _ptr(res["flags"]), B, _stream()), "swc_activity_normalise")
+    return out, res["gains"], res["flags"]
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""
