@@ -166,6 +166,7 @@ int swc_gemm_plan(const swc_gemm_args* args, swc_gemm_plan_out* plan);
  * dtype is the element type of qkv and out.
  * Memory: all T rows of out of every utterance are written and nothing else.  q / k / v rows t >= lens[b] may be read (they
  * must be finite) but rows t < lens[b] of out do not depend on them, bit for bit; an utterance with lens[b] == 0 is not read.
+ * lens[b] outside [0, T] is clamped to that range (swc_attention16 and swc_attention_ex too).  B and H are at most 65535.
  */
 int swc_attention(const void* qkv, void* out, const int32_t* lens, int32_t B, int32_t T,
                   int32_t H, int32_t dtype, void* stream);

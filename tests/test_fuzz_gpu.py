@@ -83,6 +83,13 @@ def test_attention_random_lengths(seed):
         src = qkv.double()
     lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
     out = ops.attention(dev_in, lens_d, B, T, H)
+    # the same draw packed (valid rows back to back, the buffers end at row sum(lens)): the padded result's valid rows, bit for bit
+    starts = [sum(lens[:b]) for b in range(B)]
+    packed_in = torch.cat([dev_in[b, :lens[b]] for b in range(B)]).contiguous()
+    packed = ops.attention(packed_in, lens_d, B, T, H, row_start=torch.tensor(starts, dtype=torch.int32, device=DEV), rows=sum(lens))
+    assert packed.shape == (sum(lens), out.shape[-1]) and packed.dtype == out.dtype
+    for b in range(B):
+        assert torch.equal(packed[starts[b]:starts[b] + lens[b]].view(torch.int16), out[b, :lens[b]].view(torch.int16)), (seed, b)
     if dt == torch.float16:  # split-f16 [rows, 2 D] at scale 64 -> float64
         v = out.cpu().double().view(B * T, D // 32, 2, 32)
         out = ((v[:, :, 0] + v[:, :, 1]).reshape(B, T, D)) / 64.0
