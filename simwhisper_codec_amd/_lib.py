@@ -254,6 +254,29 @@ ACTIVITY_SIGNATURES = {
     "swc_activity_normalise": ([_P, _P, _P, _D, _P, _L, _L, _P, _P, _I, _P], C.c_int),
 }
 
+# include/swc_track.h (the sub-sample lag of every segment of every pair, one line per pair, the degraded row on the clean
+# row's clock), one to one.  The thirteenth table of its own
+TRACK_W, TRACK_P = 16, 32                        # SWC_TRACK_W / _P
+TRACK_TABLE_ROWS, TRACK_TABLE_COLS = 35, 33      # SWC_TRACK_TABLE_ROWS / _COLS
+TRACK_MAX_RANGE = 1024                           # SWC_TRACK_MAX_RANGE
+TRACK_MAX_N = 1 << 22                            # SWC_TRACK_MAX_N
+TRACK_MAX_SEGMENTS = 4096                        # SWC_TRACK_MAX_SEGMENTS
+TRACK_CHUNK, TRACK_LAG_BLOCK, TRACK_SPILL = 4096, 256, 256   # SWC_TRACK_CHUNK / _LAG_BLOCK / _SPILL
+TRACK_VALUES = 4                                 # SWC_TRACK_VALUES
+TRACK_DEFINED, TRACK_EDGE = 1, 2                 # SWC_TRACK_DEFINED / _EDGE
+FIT_VALUES, FIT_COUNTS = 4, 4                    # SWC_FIT_VALUES / _COUNTS
+FIT_NO_DRIFT, FIT_NO_LAG, FIT_EDGE = 1, 2, 4     # SWC_FIT_NO_DRIFT / _NO_LAG / _EDGE
+WARP_TAPS, WARP_PHASES, WARP_BLOCK, WARP_INFO = 32, 256, 256, 4   # SWC_WARP_TAPS / _PHASES / _BLOCK / _INFO
+WARP_MAX_DRIFT = 0.01                            # SWC_WARP_MAX_DRIFT
+WARP_MAX_LAG = 1 << 23                           # SWC_WARP_MAX_LAG
+TRACK_SIGNATURES = {
+    "swc_track_segments": ([_L, _I, _I], C.c_int64),
+    "swc_lag_track_workspace_bytes": ([_I, _L, _L, _I, _I, _I], C.c_int64),
+    "swc_lag_track": ([_P, _P, _P, _P, _L, _L, _P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _L, _P, _L, _I, _P], C.c_int),
+    "swc_lag_fit": ([_P, _P, _L, _P, _I, _P, _L, _D, _I, _P, _P, _I, _P], C.c_int),
+    "swc_warp": ([_P, _P, _P, _L, _L, _P, _L, _P, _P, _L, _L, _P, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -274,7 +297,7 @@ def load():
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
-                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES):
+                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

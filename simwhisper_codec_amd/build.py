@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libswc_hip.so")
 SOURCES = ["swc_api.hip", "swc_gemm.hip", "swc_gemm_skinny.hip", "swc_attention.hip", "swc_attention16.hip", "swc_pointwise.hip", "swc_convnext.hip", "swc_mlp.hip", "swc_convnext64.hip", "swc_projln.hip",
-           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip"]
+           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip", "swc_track.hip"]
 ARCH = "gfx950"
 # per-file flags.  -fno-slp-vectorize: hipcc otherwise packs adjacent f32 mul/add/fma into v_pk_*_f32, which issue at
 # half rate on gfx950 and cost extra v_mov shuffles — slower beside MFMAs (softmax, epilogues)
@@ -25,7 +25,10 @@ _MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 EXTRA_FLAGS = {"swc_attention16.hip": ["-fno-slp-vectorize"], "swc_convnext.hip": ["-fno-slp-vectorize"] + _MAX_ILP,
                "swc_mlp.hip": ["-fno-slp-vectorize"] + _MAX_ILP, "swc_convnext64.hip": ["-fno-slp-vectorize"] + _MAX_ILP,
                "swc_projln.hip": ["-fno-slp-vectorize"] + _MAX_ILP,
-               "swc_gemm.hip": _MAX_ILP}  # (-fno-slp-vectorize measured slower for swc_gemm.hip: -10 %)
+               "swc_gemm.hip": _MAX_ILP,  # (-fno-slp-vectorize measured slower for swc_gemm.hip: -10 %)
+               # include/swc_track.h fixes the rounding of every float64 operation: no contraction anywhere in that file
+               # (its one fused chain is written as fmaf)
+               "swc_track.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():
@@ -39,7 +42,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h", "swc_track.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -168,6 +171,31 @@ def build_flac_enc_check(force=False):
         raise RuntimeError(f"building swc_flac_enc_check failed:\n{r.stdout}")
     os.replace(FLAC_ENC_CHECK_PATH + ".tmp", FLAC_ENC_CHECK_PATH)
     return FLAC_ENC_CHECK_PATH
+
+
+TRACK_CHECK_PATH = os.path.join(HERE, "swc_track_check")
+
+
+def build_track_check(force=False):
+    """swc_track_check: a stand-alone host program (its own main) over csrc/swc_track_host.h (the segment count, the workspace
+    layout and the Q32 bounds of swc_warp: the serial integer arithmetic swc_track.hip runs on the host and in its kernels)
+    compiled with -fsanitize=address,undefined (tests/test_track_cpu.py).  No GPU code, nothing preloaded."""
+    src = os.path.join(CSRC, "swc_track_check.cpp")
+    deps = [src, os.path.join(CSRC, "swc_track_host.h"), os.path.join(ROOT, "include", "swc_track.h")]
+    if not force and os.path.exists(TRACK_CHECK_PATH) and all(os.path.getmtime(f) <= os.path.getmtime(TRACK_CHECK_PATH) for f in deps):
+        return TRACK_CHECK_PATH
+    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("g++"), shutil.which("clang++")) if c), None)
+    if cxx is None:
+        raise RuntimeError("no C++ compiler found for swc_track_check (set CXX)")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+    base = [cxx, "-std=c++17", "-Wall"] + san + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, src, "-o", TRACK_CHECK_PATH + ".tmp"]
+    r = subprocess.run(base + ["-static-libasan", "-static-libubsan"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:   # a toolchain without the runtimes as archives
+        r = subprocess.run(base, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"building swc_track_check failed:\n{r.stdout}")
+    os.replace(TRACK_CHECK_PATH + ".tmp", TRACK_CHECK_PATH)
+    return TRACK_CHECK_PATH
 
 
 def stamp_commit():

@@ -108,7 +108,7 @@ def stoi_table(sample_rate, device):
     return _cached(_TABLES, sample_rate, device, build)
 
 
-def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """STOI of pair i = (ref_list[i] clean, deg_list[i] degraded), two lists of 1-D waveforms at sample_rate (host or device
     tensors); pair i is cut to its shorter length.  -> (d FloatTensor[B], segs IntTensor[B]) on `device`: the score, and the
     number of 30-frame segments it averages.  A pair too short for one segment (fewer than 30 frames of 12.8 ms are left after
@@ -121,7 +121,7 @@ def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), ali
         table = stoi_table(sample_rate, device)
         with torch.cuda.device(device):
             return ops.stoi(*_stage(ref_list, deg_list, device), table)
-    return _scored("stoi", "the metric is a HIP kernel", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms)
+    return _scored("stoi", "the metric is a HIP kernel", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
 def _stage(ref_list, deg_list, device, cut=True):
@@ -158,24 +158,30 @@ def _pairs_on(who, ref_list, deg_list, device):
     return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
 
 
-def _scored(who, what, score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=None):
+def _scored(who, what, score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine=None, check=None):
     """The way into stoi(), quality(), spectral() and pitch().  In this order, and without touching the GPU: the align= /
     max_lag_ms= check, the device check, `check()` (the call's own arguments), the pair-count check.  Then
     score(ref_list, deg_list, device with its index) -> the call's result.  With align=, the pairs are aligned first
-    (aligned(): one small read-back), their views scored and, where the result is a dict, "lag" added."""
+    (aligned(): one small read-back), their views scored and, where the result is a dict, "lag" added.  With fine= "lag" or
+    "drift" beside align= (include/swc_track.h), the degraded rows are warped onto the clean rows' clock first and "lag_fine"
+    and "drift_ppm" added as well."""
     _check_align(who, align, max_lag_ms)
+    _check_fine(who, align, fine)
     device = _cuda(who, what, device)
-    lag = None
+    extra = None
     if align is not None:
-        ref_list, deg_list, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device)
-        lag = a["lag"]
+        ref_list, deg_list, a = aligned(ref_list, deg_list, sample_rate=sample_rate, max_lag_ms=max_lag_ms, mode=align, device=device,
+                                        fine=fine)
+        extra = {"lag": a["lag"]}
+        if fine is not None:
+            extra.update(lag_fine=a["lag_fine"], drift_ppm=a["drift_ppm"])
     if check is not None:
         check()
     res = score(ref_list, deg_list, _pairs_on(who, ref_list, deg_list, device))
-    return dict(res, lag=lag) if lag is not None and isinstance(res, dict) else res
+    return dict(res, **extra) if extra is not None and isinstance(res, dict) else res
 
 
-def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS, align=None, max_lag_ms=50.0):
+def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.QUALITY_METRICS, align=None, max_lag_ms=50.0, fine=None):
     """STOI, ESTOI and SI-SDR of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_quality call: the lists, the cut
     to the shorter length and the staging of host rows are those of stoi().  `want`: which of "stoi", "estoi", "si_sdr".
     -> dict on `device`: a FloatTensor[B] per wanted metric and, when stoi or estoi is wanted, "segs" IntTensor[B] (a pair too
@@ -194,18 +200,18 @@ def quality(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), 
         table = stoi_table(sample_rate, device) if front else None
         with torch.cuda.device(device):
             return ops.quality(*_stage(ref_list, deg_list, device), table, want=want)
-    return _scored("quality", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms)
+    return _scored("quality", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
-def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def estoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """ESTOI alone: -> (d FloatTensor[B], segs IntTensor[B]), the conventions of stoi()"""
-    r = quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("estoi",), align=align, max_lag_ms=max_lag_ms)
+    r = quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("estoi",), align=align, max_lag_ms=max_lag_ms, fine=fine)
     return r["estoi"], r["segs"]
 
 
-def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def si_sdr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """SI-SDR alone, in dB: -> FloatTensor[B] (NaN for an empty pair).  sample_rate is not used by the measure: any rate works."""
-    return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",), align=align, max_lag_ms=max_lag_ms)["si_sdr"]
+    return quality(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("si_sdr",), align=align, max_lag_ms=max_lag_ms, fine=fine)["si_sdr"]
 
 
 # ---- spectral distances (include/swc_spectral.h) ----
@@ -279,7 +285,7 @@ def spectral_table(sample_rate, device):
     return _cached(_SPECTRAL_TABLES, sample_rate, device, build)
 
 
-def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0,
+def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0, fine=None,
              level=None):
     """Multi-scale mel distance, multi-resolution STFT distance and log-spectral distance of pair i = (ref_list[i] clean,
     deg_list[i] degraded) in one swc_spectral call: the lists, the cut to the shorter length and the staging of host rows are
@@ -323,23 +329,23 @@ def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"),
                 res = ops.spectral(*_stage(ref_list, deg_list, device), table, want=want)
         res["scales"] = scales
         return res
-    return _scored("spectral", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms,
+    return _scored("spectral", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine,
                    check=lambda: ops._want("spectral", want, ops.SPECTRAL_METRICS))
 
 
-def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the multi-scale mel distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",), align=align, max_lag_ms=max_lag_ms)["mel"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",), align=align, max_lag_ms=max_lag_ms, fine=fine)["mel"]
 
 
-def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the multi-resolution STFT distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",), align=align, max_lag_ms=max_lag_ms)["stft"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",), align=align, max_lag_ms=max_lag_ms, fine=fine)["stft"]
 
 
-def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0):
+def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the log-spectral distance (W = 2048) alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",), align=align, max_lag_ms=max_lag_ms)["lsd"]
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",), align=align, max_lag_ms=max_lag_ms, fine=fine)["lsd"]
 
 
 # ---- pitch (include/swc_pitch.h) ----
@@ -354,7 +360,7 @@ def _tracks(res, side):
 
 
 def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda"), want=PITCH_KEYS, tracks=False,
-          align=None, max_lag_ms=50.0):
+          align=None, max_lag_ms=50.0, fine=None):
     """F0 RMSE in cents, F0 correlation, gross pitch error, voicing decision error and V/UV F1 of pair i = (ref_list[i] clean,
     deg_list[i] degraded) in one swc_pitch call (YIN in exact integer arithmetic, include/swc_pitch.h): the lists, the cut to the
     shorter length and the staging of host rows are those of quality().  The call's parameters come from the rate
@@ -383,7 +389,7 @@ def pitch(ref_list, deg_list, sample_rate=16000, f_min=62.5, f_max=500.0, device
         if tracks:
             res["tracks_ref"], res["tracks_deg"] = _tracks(r, "x"), _tracks(r, "y")
         return res
-    return _scored("pitch", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=check)
+    return _scored("pitch", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine, check=check)
 
 
 def f0(wav_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device("cuda")):
@@ -428,14 +434,51 @@ def _check_align(who, align, max_lag_ms):
     align_range(1, max_lag_ms)
 
 
-def _align_rows(who, ref_list, deg_list, sample_rate, max_lag_ms, mode, device):
-    """the checks and the call shared by align() and aligned() -> (clean rows, degraded rows, result dict)"""
+FINE_MODES = (None, "lag", "drift")
+FINE_KEYS = ("lag_fine", "drift_ppm", "residual", "segments", "flags")
+TRACK_KEYS = ("t", "lag", "corr", "status")
+
+
+def _check_fine(who, align, fine):
+    """the fine= argument of the metric calls: None, "lag" or "drift", and only beside align="""
+    if fine not in FINE_MODES:
+        raise SwcError(f"{who}: fine={fine!r}: None, \"lag\" or \"drift\"")
+    if fine is not None and align is None:
+        raise SwcError(f"{who}: fine={fine!r} needs align= (the track starts from the integer lag)")
+
+
+def track_params(sample_rate, segment_ms=1000.0, hop_ms=500.0, track_range_ms=8.0):
+    """S, H, Rs of a swc_lag_track call in samples.  SwcError beyond the limits of include/swc_track.h"""
+    try:
+        sr, seg, hop, rng = int(sample_rate), float(segment_ms), float(hop_ms), float(track_range_ms)
+    except (TypeError, ValueError):
+        raise SwcError(f"lag_track: sample_rate={sample_rate!r}, segment_ms={segment_ms!r}, hop_ms={hop_ms!r}, track_range_ms={track_range_ms!r}")
+    if sr < 1 or not (0.0 <= seg < math.inf) or not (0.0 < hop < math.inf) or not (0.0 <= rng < math.inf):
+        raise SwcError(f"lag_track: segment_ms={segment_ms!r} (>= 0; 0: the whole row), hop_ms={hop_ms!r} (> 0), track_range_ms={track_range_ms!r} (>= 0)")
+    S, H, Rs = int(round(seg * sr / 1000.0)), max(1, int(round(hop * sr / 1000.0))), int(round(rng * sr / 1000.0))
+    if Rs > _lib.TRACK_MAX_RANGE:
+        raise SwcError(f"lag_track: track_range_ms={track_range_ms} at {sr} Hz is {Rs} samples: at most {_lib.TRACK_MAX_RANGE} (include/swc_track.h)")
+    if S > _lib.TRACK_MAX_N or H > _lib.TRACK_MAX_N:
+        raise SwcError(f"lag_track: segment_ms={segment_ms}, hop_ms={hop_ms} at {sr} Hz: at most {_lib.TRACK_MAX_N} samples (include/swc_track.h)")
+    return S, H, Rs
+
+
+def _align_rows(who, ref_list, deg_list, sample_rate, max_lag_ms, mode, device, fine=None, track=None, rho_min=0.3):
+    """the checks and the calls shared by align(), aligned() and lag_track() -> (clean rows, degraded rows, result dict).
+    fine / track: the swc_lag_track and swc_lag_fit calls behind the swc_align call, on the same stream, nothing read back"""
     if mode not in ops.ALIGN_MODES:
         raise SwcError(f"{who}: mode={mode!r}: one of {tuple(ops.ALIGN_MODES)}")
+    if fine not in FINE_MODES:
+        raise SwcError(f"{who}: fine={fine!r}: None, \"lag\" or \"drift\"")
     L = align_range(sample_rate, max_lag_ms)
+    S, H, Rs = track_params(sample_rate, *(track or ())) if (fine is not None or track is not None) else (0, 0, 0)
     device = _pairs_on(who, ref_list, deg_list, _cuda(who, "the alignment is a HIP kernel", device))
     if len(ref_list) == 0:
         res = {k: torch.zeros(0, device=device, dtype=torch.float32 if k in ("corr", "gain") else torch.int32) for k in ALIGN_KEYS}
+        if fine is not None:
+            res.update(lag_fine=torch.zeros(0, device=device, dtype=torch.float64), drift_ppm=torch.zeros(0, device=device, dtype=torch.float64),
+                       residual=torch.zeros(0, device=device, dtype=torch.float64), segments=torch.zeros((0, 2), device=device, dtype=torch.int32),
+                       flags=torch.zeros(0, device=device, dtype=torch.int32))
         return [], [], res
     for r in list(ref_list) + list(deg_list):
         if r.numel() > _lib.ALIGN_MAX_N:
@@ -443,13 +486,26 @@ def _align_rows(who, ref_list, deg_list, sample_rate, max_lag_ms, mode, device):
     with torch.cuda.device(device):
         x_rows, y_rows = _stage(ref_list, deg_list, device, cut=False)
         r = ops.align(x_rows, y_rows, L, mode, want=("info", "values"))
-    info, values = r["info"], r["values"]
-    res = {"lag": info[:, 0], "corr": values[:, 0], "gain": values[:, 1], "start_ref": info[:, 1], "start_deg": info[:, 2],
-           "length": info[:, 3]}
+        info, values = r["info"], r["values"]
+        res = {"lag": info[:, 0], "corr": values[:, 0], "gain": values[:, 1], "start_ref": info[:, 1], "start_deg": info[:, 2],
+               "length": info[:, 3]}
+        if fine is not None or track is not None:
+            tr = ops.lag_track(x_rows, y_rows, info, S, H, Rs, mode)
+            res["_track"] = tr
+        if fine is not None:
+            ft = ops.lag_fit(tr["vals"], tr["status"], tr["nseg"], info, rho_min=rho_min, drift=(fine == "drift"))
+            fit, counts = ft["fit"], ft["counts"]
+            res.update(lag_fine=fit[:, 0], drift_ppm=fit[:, 1] * 1e6, residual=fit[:, 2], segments=counts[:, 0:2], flags=counts[:, 2])
+            res["_fit"] = fit
     return x_rows, y_rows, res
 
 
-def align(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda")):
+def _public(res):
+    return {k: v for k, v in res.items() if not k.startswith("_")}
+
+
+def align(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda"), fine=None,
+          segment_ms=1000.0, hop_ms=500.0, track_range_ms=8.0, rho_min=0.3):
     """The constant delay of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_align call (include/swc_align.h): the
     integer lag d in -L .. L, L = round(max_lag_ms sample_rate / 1000), that maximises the exact int64 cross-correlation of the
     two rows (mode "waveform") or of their rectified, mean-free envelopes (mode "envelope": for pairs whose fine structure
@@ -458,18 +514,58 @@ def align(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform
     normalised correlation at that lag over the overlap; NaN for a silent or empty pair), "gain" FloatTensor[B] (the factor
     that brings the degraded row to the clean row's level over the overlap; reported, not applied), "start_ref", "start_deg",
     "length" IntTensor[B]: ref[start_ref : start_ref + length] faces deg[start_deg : start_deg + length].  Nothing is
-    synchronised."""
-    return _align_rows("align", ref_list, deg_list, sample_rate, max_lag_ms, mode, device)[2]
+    synchronised.
+    fine = "lag" or "drift" (include/swc_track.h: swc_lag_track and swc_lag_fit behind the swc_align call, same stream, nothing
+    read back): the lag of every segment of segment_ms every hop_ms, searched over +- track_range_ms round the integer lag, to
+    a fraction of a sample, and one line through them.  Adds "lag_fine" DoubleTensor[B] (the lag at the clean row's first sample,
+    fractional samples), "drift_ppm" DoubleTensor[B] (0 with "lag"), "residual" DoubleTensor[B] (weighted rms of the segments
+    round the line, samples), "segments" IntTensor[B][2] (used, offered) and "flags" IntTensor[B] (1: fewer than two usable
+    segments for a drift fit, 2: none for a lag, 4: a used segment's peak on the edge of the range; with 1 or 2, lag_fine =
+    lag and drift_ppm = 0).  The track follows a lag that stays within track_range_ms of the integer lag over the row; a
+    larger drift is reported through the flags, not guessed.  With fine=None the dict and the launches are those above."""
+    track = (segment_ms, hop_ms, track_range_ms) if fine is not None else None
+    return _public(_align_rows("align", ref_list, deg_list, sample_rate, max_lag_ms, mode, device, fine=fine, track=track, rho_min=rho_min)[2])
 
 
-def aligned(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda")):
+def lag_track(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, segment_ms=1000.0, hop_ms=500.0, track_range_ms=8.0,
+              mode="waveform", device=torch.device("cuda")):
+    """The lag of every segment of every pair (include/swc_track.h swc_lag_track behind swc_align): -> a list with one dict
+    per pair, "t" DoubleTensor[K] (the segments' centres, samples of the clean row), "lag" DoubleTensor[K] (fractional samples;
+    NaN for a segment without a peak), "corr" DoubleTensor[K], "status" IntTensor[K] (bit 0: defined, bit 1: the peak lies on
+    the edge of +- track_range_ms).  One small read-back (the B segment counts) synchronises the stream."""
+    x_rows, _, res = _align_rows("lag_track", ref_list, deg_list, sample_rate, max_lag_ms, mode, device,
+                                 track=(segment_ms, hop_ms, track_range_ms))
+    if not x_rows:
+        return []
+    tr = res["_track"]
+    out = []
+    for b, k in enumerate(tr["nseg"].cpu().tolist()):
+        v = tr["vals"][b, :k]
+        out.append({"t": v[:, 3], "lag": v[:, 0], "corr": v[:, 1], "status": tr["status"][b, :k]})
+    return out
+
+
+def aligned(ref_list, deg_list, sample_rate=16000, max_lag_ms=50.0, mode="waveform", device=torch.device("cuda"), fine=None,
+            segment_ms=1000.0, hop_ms=500.0, track_range_ms=8.0, rho_min=0.3):
     """align(), then the aligned pairs themselves: -> (ref_views, deg_views, info) with info the dict of align() and the views
     x[start_ref : start_ref + length], y[start_deg : start_deg + length] of the staged device rows: zero-copy, equal lengths
     within a pair.  ONE small read-back (the B x 4 int32 of lag, starts and length) synchronises the stream: the views' bounds
-    are host numbers."""
-    x_rows, y_rows, res = _align_rows("aligned", ref_list, deg_list, sample_rate, max_lag_ms, mode, device)
+    are host numbers.
+    fine = "lag" or "drift": the degraded rows are resampled onto the clean rows' clock along the fitted line (swc_warp: new
+    tensors, a 32-tap windowed sinc, positions in exact Q32) on the same stream, and the one read-back is the warp's B x 4
+    int32 instead: -> the clean views x[x0 : x0 + m] and the warped rows of m samples that face them."""
+    track = (segment_ms, hop_ms, track_range_ms) if fine is not None else None
+    x_rows, y_rows, res = _align_rows("aligned", ref_list, deg_list, sample_rate, max_lag_ms, mode, device, fine=fine, track=track,
+                                      rho_min=rho_min)
     if not x_rows:
-        return [], [], res
+        return [], [], _public(res)
+    if fine is not None:
+        with torch.cuda.device(x_rows[0].device):
+            w = ops.warp(y_rows, [x.numel() for x in x_rows], res["_fit"])
+        cut = w["info"][:, :2].cpu().tolist()
+        xs = [x[x0:x0 + m] for x, (x0, m) in zip(x_rows, cut)]
+        ys = [w["out"][b, :m] for b, (_, m) in enumerate(cut)]
+        return xs, ys, _public(res)
     cut = torch.stack([res["start_ref"], res["start_deg"], res["length"]], dim=1).cpu().tolist()
     xs = [x[x0:x0 + m] for x, (x0, _, m) in zip(x_rows, cut)]
     ys = [y[y0:y0 + m] for y, (_, y0, m) in zip(y_rows, cut)]
@@ -746,7 +842,7 @@ def mcd_band(sample_rate, band_ms):
     return int(round(ms / hop_ms))
 
 
-def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=False, align=None, max_lag_ms=50.0,
+def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=False, align=None, max_lag_ms=50.0, fine=None,
         device=torch.device("cuda")):
     """Mel-cepstral distortion of pair i = (ref_list[i] clean, deg_list[i] degraded) in dB, in one swc_cepstra call over the 2 B
     rows and one swc_dtw call (include/swc_mcd.h): 13 cepstral coefficients (c0 left out) of 80 mel bands, a frame every 10 ms.
@@ -786,7 +882,7 @@ def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=Fals
         if path:
             res["path"] = r["path"]
         return res
-    return _scored("mcd", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, check=check)
+    return _scored("mcd", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine, check=check)
 
 
 def dtw(feat_ref, feat_deg, band=0, device=torch.device("cuda")):

@@ -889,6 +889,178 @@ def align(x_rows, y_rows, L, mode, want=("info", "values"), max_nx=None, max_ny=
     return res
 
 
+TRACK_OUTPUTS = ("vals", "status", "nseg", "xc")
+_TRACK_TABLES = {}
+
+
+def _sinc(u):
+    import numpy as np
+    safe = np.where(u == 0, 1.0, u)
+    return np.where(u == 0, 1.0, np.sin(np.pi * safe) / (np.pi * safe))
+
+
+def track_table_host():
+    """T of include/swc_track.h in float64 on the host: [35][33], T[j + 17][t + 16] = sinc(t - j / 32) Hann over +-17"""
+    import numpy as np
+    W, P = _lib.TRACK_W, _lib.TRACK_P
+    j = np.arange(-P // 2 - 1, P // 2 + 2, dtype=np.float64)[:, None]
+    t = np.arange(-W, W + 1, dtype=np.float64)[None, :]
+    u = t - j / P
+    return torch.from_numpy(_sinc(u) * (0.5 + 0.5 * np.cos(np.pi * u / (W + 1))))
+
+
+def warp_table_host():
+    """H of include/swc_track.h: f32 [257][32], H[p][t + 15] = sinc(t - p / 256) Hann over +-16, rounded once from float64"""
+    import numpy as np
+    p = np.arange(_lib.WARP_PHASES + 1, dtype=np.float64)[:, None]
+    t = np.arange(-15, 17, dtype=np.float64)[None, :]
+    u = t - p / _lib.WARP_PHASES
+    return torch.from_numpy((_sinc(u) * (0.5 + 0.5 * np.cos(np.pi * u / 16))).astype(np.float32))
+
+
+def _track_tables(device):
+    """the two host-built tables on `device`, uploaded once per device"""
+    key = (device.type, device.index)
+    if key not in _TRACK_TABLES:
+        _TRACK_TABLES[key] = (track_table_host().to(device).contiguous(), warp_table_host().to(device).contiguous())
+    return _TRACK_TABLES[key]
+
+
+def track_segments(n, S, H):
+    """swc_track_segments of include/swc_track.h"""
+    v = int(_lib.load().swc_track_segments(int(n), int(S), int(H)))
+    if v < 0:
+        raise _lib.SwcError(f"lag_track: no segment count for n={n}, S={S}, H={H}")
+    return v
+
+
+def lag_track_workspace_bytes(B, max_nx, max_ny, S, H, Rs):
+    """swc_lag_track_workspace_bytes of include/swc_track.h"""
+    v = int(_lib.load().swc_lag_track_workspace_bytes(int(B), int(max_nx), int(max_ny), int(S), int(H), int(Rs)))
+    if v < 0:
+        raise _lib.SwcError(f"lag_track: no workspace size for B={B}, max_nx={max_nx}, max_ny={max_ny}, S={S}, H={H}, Rs={Rs} "
+                            f"(Rs <= {_lib.TRACK_MAX_RANGE}, rows <= {_lib.TRACK_MAX_N}, at most {_lib.TRACK_MAX_SEGMENTS} segments)")
+    return v
+
+
+def _d0_column(who, d0, B):
+    """the centre lags as (tensor, stride): an int32 device tensor [B] or [B][n] (column 0 is read: swc_align's info as it is)"""
+    _chk(d0, f"{who} d0", torch.int32)
+    if d0.dim() not in (1, 2) or d0.shape[0] != B or not d0.is_contiguous() or d0.numel() == 0:
+        raise _lib.SwcError(f"{who}: d0 is a contiguous int32 tensor [B] or [B][n] (column 0 is the centre lag)")
+    return d0, (1 if d0.dim() == 1 else d0.shape[1])
+
+
+def lag_track(x_rows, y_rows, d0, S, H, Rs, mode, want=("vals", "status", "nseg"), max_nx=None, max_ny=None, ldk=None, ldc=None,
+              out=None, workspace=None, table=None):
+    """The sub-sample lag of every segment of every (clean, degraded) pair (include/swc_track.h swc_lag_track).  d0: int32
+    device tensor [B] or [B][n] (column 0: swc_align's info as it is); S, H = segment length and hop in samples of x (S == 0:
+    the whole row); Rs = the search half-range; mode as in align.  -> dict of the wanted outputs: vals f64 [B][ldk][4] = lag,
+    rho, weight, centre; status int32 [B][ldk]; nseg int32 [B]; xc int64 [B][ldk][ldc] (c_k[d] at column d + Rs + 17); plus
+    "K", the host's bound on the segments.  Slots at and beyond K and columns at and beyond 2 (Rs + 17) + 1 are not written
+    (the tensors come from torch.zeros).  max_nx, max_ny, ldk, ldc, out, workspace, table (tests) as in align."""
+    lib = _lib.load()
+    want = _want("lag_track", want, TRACK_OUTPUTS, may_be_empty=True)
+    if mode not in ALIGN_MODES:
+        raise _lib.SwcError(f"lag_track: mode={mode!r}: one of {tuple(ALIGN_MODES)}")
+    S, H, Rs = int(S), int(H), int(Rs)
+    if not 0 <= Rs <= _lib.TRACK_MAX_RANGE:
+        raise _lib.SwcError(f"lag_track: search half-range Rs={Rs} (0..{_lib.TRACK_MAX_RANGE})")
+    if S < 0 or (S > 0 and H < 1):
+        raise _lib.SwcError(f"lag_track: segment length S={S}, hop H={H} (S >= 0; H >= 1 with S > 0)")
+    n_x, n_y, device = _pair_rows("lag_track", x_rows, y_rows, equal_lengths=False)
+    B = len(n_x)
+    d0, ld_d0 = _d0_column("lag_track", d0, B)
+    max_nx = max(n_x) if max_nx is None else int(max_nx)
+    max_ny = max(n_y) if max_ny is None else int(max_ny)
+    workspace = _workspace("lag_track", lag_track_workspace_bytes(B, max_nx, max_ny, S, H, Rs), workspace, device)
+    K = track_segments(max_nx, S, H)
+    nl = 2 * (Rs + _lib.TRACK_W + 1) + 1
+    ldk = max(K, 1) if ldk is None else int(ldk)
+    ldc = nl if ldc is None else int(ldc)
+    shapes = {"vals": ((B, ldk, _lib.TRACK_VALUES), torch.float64), "status": ((B, ldk), torch.int32), "nseg": ((B,), torch.int32),
+              "xc": ((B, ldk, ldc), torch.int64)}
+    res = _outputs("lag_track", {name: shapes[name] for name in want}, out, device, torch.zeros)
+    table = _track_tables(device)[0] if table is None else _chk(table, "lag_track table", torch.float64)
+    if table.numel() != _lib.TRACK_TABLE_ROWS * _lib.TRACK_TABLE_COLS or not table.is_contiguous():
+        raise _lib.SwcError("lag_track: the table is a contiguous f64 tensor [35][33]")
+    xp, yp, nx, ny = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_x, n_y)
+    _lib.check(lib.swc_lag_track(_ptr(xp), _ptr(yp), _ptr(nx), _ptr(ny), max_nx, max_ny, _ptr(d0), ld_d0, S, H, Rs, ALIGN_MODES[mode],
+                                 _ptr(table), _ptr(res.get("vals")), _ptr(res.get("status")), ldk, _ptr(res.get("nseg")),
+                                 _ptr(res.get("xc")), ldc, _ptr(workspace), workspace.numel(), B, _stream()), "swc_lag_track")
+    res["K"] = K
+    return res
+
+
+def lag_fit(vals, status, nseg, d0, rho_min=0.3, drift=True, kmax=None, out=None):
+    """One line lag(t) = a + b t per pair through its track (include/swc_track.h swc_lag_fit): vals f64 [B][ldk][4], status
+    int32 [B][ldk], nseg int32 [B] as lag_track wrote them, d0 as there.  -> dict(fit f64 [B][4] = a, b, rms, 0; counts int32
+    [B][4] = used, offered, flags, 0).  kmax (tests): the host's bound on nseg, default ldk."""
+    lib = _lib.load()
+    _chk(vals, "lag_fit vals", torch.float64)
+    _chk(status, "lag_fit status", torch.int32)
+    _chk(nseg, "lag_fit nseg", torch.int32)
+    if vals.dim() != 3 or vals.shape[2] != _lib.TRACK_VALUES or tuple(status.shape) != tuple(vals.shape[:2]) or \
+            tuple(nseg.shape) != (vals.shape[0],) or not (vals.is_contiguous() and status.is_contiguous() and nseg.is_contiguous()):
+        raise _lib.SwcError("lag_fit: vals [B][ldk][4], status [B][ldk] and nseg [B] are contiguous tensors of one B and ldk")
+    B, ldk = vals.shape[0], vals.shape[1]
+    if B == 0:
+        raise _lib.SwcError("lag_fit: no pair")
+    d0, ld_d0 = _d0_column("lag_fit", d0, B)
+    kmax = ldk if kmax is None else int(kmax)
+    rho_min = float(rho_min)
+    if not -1.0 <= rho_min <= 1.0:
+        raise _lib.SwcError(f"lag_fit: rho_min={rho_min} (-1..1)")
+    res = _outputs("lag_fit", {"fit": ((B, _lib.FIT_VALUES), torch.float64), "counts": ((B, _lib.FIT_COUNTS), torch.int32)}, out,
+                   vals.device, torch.empty)
+    _lib.check(lib.swc_lag_fit(_ptr(vals), _ptr(status), ldk, _ptr(nseg), kmax, _ptr(d0), ld_d0, rho_min, 1 if drift else 0,
+                               _ptr(res["fit"]), _ptr(res["counts"]), B, _stream()), "swc_lag_fit")
+    return res
+
+
+def warp(y_rows, n_x, fit, cols=None, max_nx=None, max_ny=None, ld_out=None, out=None, table=None):
+    """The degraded rows on the clean rows' clock (include/swc_track.h swc_warp).  y_rows: list of 1-D f32 device tensors; n_x:
+    the clean rows' lengths; fit: an f64 device tensor [B][n >= 2] with a, b in columns 0 and 1 (lag_fit's output as it is), or
+    a list of (a, b) host pairs, each checked here: |a| <= 2^23, |b| <= 0.01.  -> dict(out f32 [B][ld_out], info int32 [B][4]
+    = x0, m, flag, 0): x[x0 .. x0 + m) faces out[0 .. m), columns [m, cols) are zero, columns at and beyond cols are not
+    written (the tensor comes from torch.zeros).  cols defaults to max(n_x)."""
+    lib = _lib.load()
+    pairs = None
+    if not torch.is_tensor(fit):     # host numbers are refused here, before anything touches the device
+        pairs = [(float(a), float(b)) for a, b in fit]
+        for a, b in pairs:
+            if not abs(b) <= _lib.WARP_MAX_DRIFT:
+                raise _lib.SwcError(f"warp: drift b={b} (|b| <= {_lib.WARP_MAX_DRIFT})")
+            if not abs(a) <= _lib.WARP_MAX_LAG:
+                raise _lib.SwcError(f"warp: lag a={a} (|a| <= {_lib.WARP_MAX_LAG})")
+    n_y, _, device = _pair_rows("warp", y_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_y)
+    n_x = [int(v) for v in n_x]
+    if len(n_x) != B:
+        raise _lib.SwcError(f"warp: {B} degraded rows and {len(n_x)} clean lengths")
+    if pairs is not None:
+        if len(pairs) != B:
+            raise _lib.SwcError(f"warp: {B} degraded rows and {len(pairs)} (a, b) pairs")
+        fit = torch.tensor(pairs, dtype=torch.float64).to(device, non_blocking=True)
+    _chk(fit, "warp fit", torch.float64)
+    if fit.dim() != 2 or fit.shape[0] != B or fit.shape[1] < 2 or not fit.is_contiguous():
+        raise _lib.SwcError("warp: fit is a contiguous f64 tensor [B][n >= 2] (a, b in columns 0 and 1)")
+    max_nx = max(n_x) if max_nx is None else int(max_nx)
+    max_ny = max(n_y) if max_ny is None else int(max_ny)
+    cols = max(n_x) if cols is None else int(cols)
+    ld_out = max(cols, 1) if ld_out is None else int(ld_out)
+    if not 0 <= cols <= _lib.TRACK_MAX_N:
+        raise _lib.SwcError(f"warp: cols={cols} (0..{_lib.TRACK_MAX_N})")
+    res = _outputs("warp", {"out": ((B, ld_out), torch.float32), "info": ((B, _lib.WARP_INFO), torch.int32)}, out, device, torch.zeros)
+    table = _track_tables(device)[1] if table is None else _chk(table, "warp table", torch.float32)
+    if table.numel() != (_lib.WARP_PHASES + 1) * _lib.WARP_TAPS or not table.is_contiguous():
+        raise _lib.SwcError("warp: the table is a contiguous f32 tensor [257][32]")
+    yp, nx, ny = _row_table(device, [r.data_ptr() for r in y_rows], n_x, n_y)
+    _lib.check(lib.swc_warp(_ptr(yp), _ptr(nx), _ptr(ny), max_nx, max_ny, _ptr(fit), fit.shape[1], _ptr(table), _ptr(res["out"]),
+                            ld_out, cols, _ptr(res["info"]), B, _stream()), "swc_warp")
+    return res
+
+
 CEPSTRA_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
 DTW_OUTPUTS = ("total", "info", "mean", "path")
 DTW_MODES = {"warp": _lib.DTW_WARP, "diagonal": _lib.DTW_DIAGONAL}

@@ -11,6 +11,13 @@ short to score (segs == 0) are listed by name and left out of the mean.
 finds every pair's constant delay first (metrics.aligned, include/swc_align.h) and scores the aligned views: for the output of
 another codec or processing chain.  The summary then adds the mean and the largest |lag| and names the pairs whose correlation
 at the chosen lag is <= 0 or not defined: those were scored, but nothing says they were aligned.
+
+    ... --align waveform --align_fine {none,lag,drift}
+
+refines the delay to a fraction of a sample ("lag") or to a line with a clock drift ("drift") and resamples the reconstruction
+onto the original's clock before it is scored (metrics.aligned(fine=...), include/swc_track.h).  The summary then adds the mean
+|drift| in ppm and names the pairs whose fit raised a flag (too few usable segments: scored at the integer lag; or a peak on
+the edge of the track's range).
 """
 import argparse
 import os
@@ -33,22 +40,52 @@ def build_parser():
 
 
 def add_align_arguments(p):
-    """the two alignment flags shared by the four evaluate tools"""
+    """the alignment flags shared by the evaluate tools"""
     p.add_argument("--align", choices=("none", "waveform", "envelope"), default="none",
                    help="find every pair's constant delay first and score the aligned views (default: the files as they are)")
     p.add_argument("--max_lag_ms", type=float, default=50.0, help="search range of --align, in milliseconds either way")
+    p.add_argument("--align_fine", choices=("none", "lag", "drift"), default="none",
+                   help="with --align: refine the delay to a fraction of a sample (lag) or to a line with a clock drift (drift) and "
+                        "resample the reconstruction onto the original's clock before scoring")
 
 
-def align_pairs(args, ref, deg, dev, lags, corrs):
+def fine_mode(args):
+    """--align_fine as the fine= argument of metrics.aligned; it needs --align"""
+    fine = getattr(args, "align_fine", "none")
+    if fine == "none":
+        return None
+    if args.align == "none":
+        raise SystemExit("--align_fine needs --align waveform or --align envelope")
+    return fine
+
+
+def align_pairs(args, ref, deg, dev, lags, corrs, fine_stats=None):
     """with --align: the aligned views of a batch (metrics.aligned), its lags and correlations appended to `lags`, `corrs`;
-    without: the batch as it is"""
+    without: the batch as it is.  With --align_fine the degraded rows come back warped, and (drift in ppm, flags) of every
+    pair is appended to `fine_stats`"""
     if args.align == "none":
         return ref, deg
     from simwhisper_codec_amd import metrics
-    xs, ys, a = metrics.aligned(ref, deg, sample_rate=args.sample_rate, max_lag_ms=args.max_lag_ms, mode=args.align, device=dev)
+    fine = fine_mode(args)
+    xs, ys, a = metrics.aligned(ref, deg, sample_rate=args.sample_rate, max_lag_ms=args.max_lag_ms, mode=args.align, device=dev, fine=fine)
     lags += [int(v) for v in a["lag"].cpu()]
     corrs += [float(v) for v in a["corr"].cpu()]
+    if fine is not None and fine_stats is not None:
+        fine_stats += list(zip((float(v) for v in a["drift_ppm"].cpu()), (int(v) for v in a["flags"].cpu())))
     return xs, ys
+
+
+def format_fine(names, fine_stats):
+    """the summary lines of an --align_fine run: the mean |drift| and the pairs whose fit raised a flag"""
+    drifts = [abs(d) for d, _ in fine_stats]
+    lines = [f"fine alignment: mean |drift| {sum(drifts) / max(len(drifts), 1):.3f} ppm, largest |drift| {max(drifts, default=0.0):.3f} ppm"]
+    bad = [n for n, (_, f) in zip(names, fine_stats) if f & 3]
+    edge = [n for n, (_, f) in zip(names, fine_stats) if f & 4 and not f & 3]
+    if bad:
+        lines.append(f"no fine fit, scored at the integer lag ({len(bad)}): " + ", ".join(bad))
+    if edge:
+        lines.append(f"a peak on the edge of the track's range ({len(edge)}): " + ", ".join(edge))
+    return lines
 
 
 def format_alignment(names, lags, corrs):
@@ -98,17 +135,18 @@ def score_batches(args, score):
     if not pairs:
         raise SystemExit("no audio files")
     dev = torch.device("cuda", torch.cuda.current_device())
-    names, cols, lags, corrs = [], {}, [], []
+    names, cols, lags, corrs, fine_stats = [], {}, [], [], []
+    fine_mode(args)
     for i in range(0, len(pairs), max(args.batch_size, 1)):
         chunk = pairs[i:i + max(args.batch_size, 1)]
         ref = [load_first_channel(o, args.sample_rate) for o, _ in chunk]
         deg = [load_first_channel(s, args.sample_rate) for _, s in chunk]
-        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs)
+        ref, deg = align_pairs(args, ref, deg, dev, lags, corrs, fine_stats)
         for k, v in score(ref, deg, dev).items():
             cols.setdefault(k, []).extend(v.cpu().tolist())
         names += [os.path.basename(o) for o, _ in chunk]
     if args.align != "none":
-        for line in format_alignment(names, lags, corrs):
+        for line in format_alignment(names, lags, corrs) + (format_fine(names, fine_stats) if fine_stats else []):
             print(line)
     return names, cols, lags, corrs
 
