@@ -277,6 +277,16 @@ TRACK_SIGNATURES = {
     "swc_warp": ([_P, _P, _P, _L, _L, _P, _L, _P, _P, _L, _L, _P, _I, _P], C.c_int),
 }
 
+# include/swc_segmental.h (LLR, Itakura-Saito, LPC cepstral distance, segmental and frequency-weighted segmental SNR in one
+# call), one to one.  The fourteenth table of its own
+SEGMENTAL_MIN_WIN, SEGMENTAL_MAX_WIN = 64, 2048  # SWC_SEGMENTAL_MIN_WIN / _MAX_WIN
+SEGMENTAL_MAX_ORDER, SEGMENTAL_MAX_BANDS = 32, 64   # SWC_SEGMENTAL_MAX_ORDER / _MAX_BANDS
+SEGMENTAL_VALUES, SEGMENTAL_MEASURES = 8, 5      # SWC_SEGMENTAL_VALUES / _MEASURES
+SEGMENTAL_SIGNATURES = {
+    "swc_segmental_workspace_bytes": ([_I, _L, _I, _I, _I], C.c_int64),
+    "swc_segmental": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _L, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -297,7 +307,7 @@ def load():
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
-                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES):
+                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

@@ -1574,6 +1574,24 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
+    def segmental(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), want=("llr", "is", "cd", "segsnr", "fwsegsnr"),
+                  tracks=False):
+        """spectral() for the LPC-domain and segmental measures: encode -> decode -> metrics.segmental of the reconstruction
+        against the input.  -> dict on the model's device: "llr", "is", "cd", "segsnr", "fwsegsnr" (DoubleTensor[B] each, as
+        wanted), "frames", "frames_lpc", "frames_fw" (IntTensor[B]) and, with tracks, "track"."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("segmental: the metrics are HIP kernels (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        return metrics.segmental(wav_list, syn, sample_rate=self.input_sample_rate, device=dev, want=want, tracks=tracks)
+
+    @_on_model_device
+    @torch.inference_mode()
     def pitch(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), f_min=62.5, f_max=500.0, tracks=False):
         """quality() for the pitch measures: encode -> decode -> metrics.pitch of the reconstruction against the input.
         -> dict on the model's device: "f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1", "voiced_ref", "voiced_deg"

@@ -37,6 +37,11 @@ them usable on the output of another codec or processing chain.  An aligned pair
 
 say how loud a row is (include/swc_loudness.h): BS.1770-4 integrated loudness, EBU Tech 3342 loudness range, sample and true
 peak, and the gain that normalises a row, computed and applied on the device.
+
+    s = metrics.segmental(ref_list, deg_list, sample_rate=16000)    # {"llr", "is", "cd", "segsnr", "fwsegsnr", "frames", ...}
+
+gives the LPC-domain and segmental measures (include/swc_segmental.h): log-likelihood ratio, Itakura-Saito distance, LPC
+cepstral distance, segmental and frequency-weighted segmental SNR, per row and (tracks=True) per frame.
 """
 import math
 
@@ -776,6 +781,113 @@ def level_normalised(wav_list, sample_rate, target_dbov=-26.0, margin_db=15.9, h
         values = ops.activity(rows, sample_rate, margin_db, hangover_ms / 1000.0)["values"]
         out, gains, flags = ops.activity_normalise(rows, values, target_dbov)
     return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+
+
+# ---- LPC-domain and segmental measures (include/swc_segmental.h) ----
+
+SEGMENTAL_KEYS = ("llr", "is", "cd", "segsnr", "fwsegsnr")
+SEGMENTAL_BANDS = 25
+
+
+def segmental_params(sample_rate):
+    """-> (W, P): the window is 30 ms rounded up to a power of two (256 at 8 kHz, 512 at 16 kHz, 2048 at 44.1 / 48 kHz), the LPC
+    order 10 below 10 kHz and 16 from there on.  SwcError for a rate whose window leaves include/swc_segmental.h's range"""
+    try:
+        sr = int(sample_rate)
+    except (TypeError, ValueError):
+        raise SwcError(f"segmental: sample_rate={sample_rate!r}")
+    if sr < 1:
+        raise SwcError(f"segmental: sample_rate={sample_rate!r}")
+    W = 1 << max(int(math.ceil(0.030 * sr)) - 1, 0).bit_length()
+    if W not in ops.SEGMENTAL_WINDOWS:
+        raise SwcError(f"segmental: sample_rate={sr} gives a window of {W} samples: windows of {ops.SEGMENTAL_WINDOWS} "
+                       "(include/swc_segmental.h)")
+    return W, (10 if sr < 10000 else 16)
+
+
+_SEGMENTAL_TABLES = {}
+
+
+def segmental_table(sample_rate, device):
+    """The bands of fwSegSNR at sample_rate on one device, built once and kept: 25 Slaney mel triangles over 0 .. fs / 2 on the
+    bins of segmental_params' window (mel_filterbank, pack_filterbanks): the `table` of ops.segmental"""
+    def build(device):
+        W, P = segmental_params(sample_rate)
+        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, SEGMENTAL_BANDS)])
+        t = {"W": W, "P": P, "K": SEGMENTAL_BANDS, "sample_rate": int(sample_rate)}
+        for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
+            t[name] = torch.from_numpy(v).to(device)
+        return t
+    return _cached(_SEGMENTAL_TABLES, sample_rate, device, build)
+
+
+def segmental(ref_list, deg_list, sample_rate=16000, want=SEGMENTAL_KEYS, tracks=False, align=None, max_lag_ms=50.0, fine=None,
+              device=torch.device("cuda")):
+    """Log-likelihood ratio, Itakura-Saito distance, LPC cepstral distance (dB), segmental SNR (dB) and frequency-weighted
+    segmental SNR (dB) of pair i = (ref_list[i] clean, deg_list[i] degraded) in one swc_segmental call (include/swc_segmental.h):
+    the lists, the cut to the shorter length and the staging of host rows are those of quality().  Frames of segmental_params'
+    window every quarter of it; llr and cd are the means of the 95 % smallest frame values, as in the literature.  `want`:
+    which of SEGMENTAL_KEYS (without "fwsegsnr" its FFT and bands are not run at all).  -> dict on `device`: a float64 tensor
+    [B] per wanted key, "frames", "frames_lpc" (frames with signal on both sides: the ones llr, is and cd see), "frames_fw"
+    IntTensor[B]; with tracks=True also "track": per pair a float64 tensor [T][5] (llr, is, cd, segsnr, fwsegsnr of every frame,
+    NaN where a frame is left out: where the reconstruction fails; one small read-back of the frame counts).  NaN where a
+    value has no frame.  The spectra are not level-normalised: a level error counts (level_matched() removes it).  align =
+    "waveform" or "envelope": the pairs are aligned first (aligned(): one small read-back), their views scored and "lag"
+    IntTensor[B] added; None: the rows as given."""
+    want, params = tuple(want), {}
+
+    def check():
+        ops._want("segmental", want, SEGMENTAL_KEYS)
+        params["W"], params["P"] = segmental_params(sample_rate)
+
+    def score(ref_list, deg_list, device):
+        if len(ref_list) == 0:
+            res = {w: torch.zeros(0, device=device, dtype=torch.float64) for w in want}
+            res.update({k: torch.zeros(0, device=device, dtype=torch.int32) for k in ("frames", "frames_lpc", "frames_fw")})
+            if tracks:
+                res["track"] = []
+            return res
+        table = segmental_table(sample_rate, device) if "fwsegsnr" in want else None
+        with torch.cuda.device(device):
+            r = ops.segmental(*_stage(ref_list, deg_list, device), params["W"], params["P"], table=table, track=tracks)
+        v = r["vals"]
+        res = {w: v[:, SEGMENTAL_KEYS.index(w)] for w in want}
+        for i, k in enumerate(("frames", "frames_lpc", "frames_fw")):
+            res[k] = v[:, 5 + i].to(torch.int32)
+        if tracks:
+            res["track"] = [r["track"][b, :T] for b, T in enumerate(res["frames"].cpu().tolist())]
+        return res
+    return _scored("segmental", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine,
+                   check=check)
+
+
+def _segmental_one(key, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine):
+    return segmental(ref_list, deg_list, sample_rate=sample_rate, want=(key,), align=align, max_lag_ms=max_lag_ms, fine=fine, device=device)[key]
+
+
+def llr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
+    """the log-likelihood ratio alone: -> DoubleTensor[B] (NaN for a pair without an LPC frame)"""
+    return _segmental_one("llr", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
+
+
+def itakura_saito(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
+    """the Itakura-Saito distance alone: -> DoubleTensor[B] (NaN for a pair without an LPC frame)"""
+    return _segmental_one("is", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
+
+
+def lpc_cd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
+    """the LPC cepstral distance alone, in dB: -> DoubleTensor[B] (NaN for a pair without an LPC frame)"""
+    return _segmental_one("cd", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
+
+
+def seg_snr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
+    """the segmental SNR alone, in dB: -> DoubleTensor[B] (NaN for a pair without a frame)"""
+    return _segmental_one("segsnr", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
+
+
+def fw_seg_snr(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
+    """the frequency-weighted segmental SNR alone, in dB: -> DoubleTensor[B] (NaN for a pair without a frame)"""
+    return _segmental_one("fwsegsnr", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
 # ---- mel-cepstral distortion (include/swc_mcd.h) ----

@@ -1357,6 +1357,75 @@ def activity_normalise(x_rows, values, target_db=-26.0, cols=None, out=None):
     return out, res["gains"], res["flags"]
 
 
+SEGMENTAL_VALUES = ("llr", "is", "cd", "segsnr", "fwsegsnr", "frames", "frames_lpc", "frames_fw")
+SEGMENTAL_WINDOWS = (64, 128, 256, 512, 1024, 2048)
+
+
+def segmental_frames(n, W):
+    """T of include/swc_segmental.h: whole frames of W samples every W / 4"""
+    return 1 + (int(n) - W) // (W // 4) if n >= W else 0
+
+
+def _segmental_params(W, P, K):
+    try:
+        W, P, K = int(W), int(P), int(K)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"segmental: W={W!r}, P={P!r}, K={K!r}")
+    if W not in SEGMENTAL_WINDOWS or not 1 <= P <= _lib.SEGMENTAL_MAX_ORDER or not 0 <= K <= _lib.SEGMENTAL_MAX_BANDS:
+        raise _lib.SwcError(f"segmental: W={W} (one of {SEGMENTAL_WINDOWS}), P={P} (1..{_lib.SEGMENTAL_MAX_ORDER}), K={K} "
+                            f"(0..{_lib.SEGMENTAL_MAX_BANDS}) (include/swc_segmental.h)")
+    return W, P, K
+
+
+def segmental_workspace_bytes(B, max_n_in, W, P, K=0):
+    """swc_segmental_workspace_bytes of include/swc_segmental.h"""
+    W, P, K = _segmental_params(W, P, K)
+    v = int(_lib.load().swc_segmental_workspace_bytes(int(B), int(max_n_in), W, P, K))
+    if v < 0:
+        raise _lib.SwcError(f"segmental: no workspace size for B={B}, max_n_in={max_n_in}, W={W}, P={P}, K={K}")
+    return v
+
+
+def segmental(x_rows, y_rows, W, P, table=None, track=False, max_n_in=None, ld_t=None, out=None, workspace=None):
+    """LLR, Itakura-Saito, LPC cepstral distance, segmental SNR and frequency-weighted segmental SNR of a ragged batch in one
+    call (include/swc_segmental.h swc_segmental): x_rows / y_rows = lists of 1-D f32 device tensors, pair b of equal length;
+    W the window, P the LPC order; `table` = the packed bands of fwSegSNR ("first", "count", "off" int32 and "w" f32 device
+    tensors, K = their length; metrics.segmental_table) or None: no fwSegSNR work, fwsegsnr NaN.  -> dict: "vals" float64
+    [B][8] in the order of SEGMENTAL_VALUES and, with track, "track" float64 [B][ld_t][5] (llr, is, cd, segsnr, fwsegsnr of
+    every frame; NaN where a frame is left out of a measure; rows beyond a pair's frame count keep zeros, or what a tensor of
+    `out` held).  max_n_in, ld_t, out, workspace (tests): the host's length bound, the track's frame capacity, a dict of
+    tensors to write under the same names and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    n_in, _, device = _pair_rows("segmental", x_rows, y_rows, equal_lengths=True)
+    B = len(n_in)
+    K = 0
+    if table is not None:
+        for name in ("first", "count", "off"):
+            _chk(table[name], f"segmental table {name}", torch.int32)
+            if table[name].numel() != table["first"].numel() or not table[name].is_contiguous():
+                raise _lib.SwcError(f"segmental: table {name} holds one contiguous entry per band")
+        _chk(table["w"], "segmental table w", torch.float32)
+        if not table["w"].is_contiguous():
+            raise _lib.SwcError("segmental: the table's weights are contiguous")
+        K = table["first"].numel()
+    W, P, K = _segmental_params(W, P, K)
+    max_n = max(n_in) if max_n_in is None else int(max_n_in)
+    workspace = _workspace("segmental", segmental_workspace_bytes(B, max_n, W, P, K), workspace, device)
+    out = out or {}
+    res = _outputs("segmental", {"vals": ((B, _lib.SEGMENTAL_VALUES), torch.float64)}, out, device, torch.empty)
+    cap = 0
+    if track:
+        cap = max(segmental_frames(min(max(n, 0), max_n), W) for n in n_in) if ld_t is None else int(ld_t)
+        res.update(_outputs("segmental", {"track": ((B, cap, _lib.SEGMENTAL_MEASURES), torch.float64)}, out, device, torch.zeros))
+    xp, yp, n = _row_table(device, [r.data_ptr() for r in x_rows], [r.data_ptr() for r in y_rows], n_in)
+    t = table if K > 0 else None
+    _lib.check(lib.swc_segmental(_ptr(xp), _ptr(yp), _ptr(n), max_n, W, P, K, _ptr(t["first"] if t else None),
+                                 _ptr(t["count"] if t else None), _ptr(t["off"] if t else None), _ptr(t["w"] if t else None),
+                                 t["w"].numel() if t else 0, _ptr(res["vals"]), _ptr(res.get("track")), cap, _ptr(workspace),
+                                 workspace.numel(), B, _stream()), "swc_segmental")
+    return res
+
+
 def set_saturation_counter(counters):
     """counters: int32/uint32 device tensor of 2 elements (or None): see swc_set_saturation_counter in include/swc.h.
     The pointer is per calling thread; the tensor must outlive its use."""
