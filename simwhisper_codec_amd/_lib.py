@@ -287,6 +287,20 @@ SEGMENTAL_SIGNATURES = {
     "swc_segmental": ([_P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _L, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_subdtw.h (per-row cepstral mean / variance normalisation, and the subsequence DTW of every patch of every feature
+# pair with the pair's median: a score after WARP-Q), one to one.  The fifteenth table of its own
+SUBDTW_MAX_PATCH = 256                           # SWC_SUBDTW_MAX_PATCH
+SUBDTW_MAX_STEPS, SUBDTW_MAX_STRIDE = 4, 3       # SWC_SUBDTW_MAX_STEPS / _MAX_STRIDE
+SUBDTW_MAX_FRAMES, SUBDTW_MAX_D = 8192, 32       # SWC_SUBDTW_MAX_FRAMES / _MAX_D
+SUBDTW_INFO = 4                                  # SWC_SUBDTW_INFO
+SUBDTW_ST_OK, SUBDTW_ST_UNREACHABLE, SUBDTW_ST_UNDEFINED, SUBDTW_ST_QUERY = 0, 1, 2, 3   # SWC_SUBDTW_ST_*
+CMVN_BLOCK = 256                                 # SWC_CMVN_BLOCK
+SUBDTW_SIGNATURES = {
+    "swc_cmvn": ([_P, _P, _I, _I, _L, _P, _L, _I, _P], C.c_int),
+    "swc_subdtw_workspace_bytes": ([_I, _I, _I, _I, _I], C.c_int64),
+    "swc_subdtw": ([_P, _P, _P, _P, _I, _I, _I, _L, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _L, _P, _P, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -307,7 +321,7 @@ def load():
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
-                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES):
+                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

@@ -1670,6 +1670,24 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
+    def warpq(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), patch_ms=400.0, steps=None, vad=True, tracks=False):
+        """quality() for the score after WARP-Q: encode -> decode -> metrics.warpq of the reconstruction against the input.
+        -> dict on the model's device: "warpq" (DoubleTensor[B], lower is better), "patches" (IntTensor[B][2] = ok, offered),
+        "frames_ref", "frames_deg" (IntTensor[B]) and, with tracks, "cost", "start", "end" per patch."""
+        from . import metrics
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError("warpq: the metrics are HIP kernels (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        return metrics.warpq(wav_list, syn, sample_rate=self.input_sample_rate, patch_ms=patch_ms,
+                             steps=metrics.WARPQ_STEPS if steps is None else steps, vad=vad, tracks=tracks, device=dev)
+
+    @_on_model_device
+    @torch.inference_mode()
     def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
         """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
         11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one

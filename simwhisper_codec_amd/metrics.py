@@ -42,6 +42,12 @@ peak, and the gain that normalises a row, computed and applied on the device.
 
 gives the LPC-domain and segmental measures (include/swc_segmental.h): log-likelihood ratio, Itakura-Saito distance, LPC
 cepstral distance, segmental and frequency-weighted segmental SNR, per row and (tracks=True) per frame.
+
+    w = metrics.warpq(ref_list, deg_list, sample_rate=16000)        # {"warpq", "patches", "frames_ref", "frames_deg"}
+    r = metrics.subsequence_dtw(query_feats, ref_feats)             # where in each recording does each snippet occur
+
+score output that is plausible speech, locally displaced and re-synthesised, not a degraded copy (include/swc_subdtw.h): a raw
+alignment cost after WARP-Q, by subsequence DTW of short patches of normalised cepstra; lower is better.
 """
 import math
 
@@ -238,15 +244,18 @@ def _hz_to_mel(f):
     return np.where(f < 1000.0, f / (200.0 / 3.0), 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (math.log(6.4) / 27.0))
 
 
-def mel_filterbank(sample_rate, W, n_mels):
+def mel_filterbank(sample_rate, W, n_mels, f_max=None):
     """-> float64 [n_mels][W / 2 + 1]: triangles on the bin frequencies f sample_rate / W between n_mels + 2 points equally
-    spaced in mel (Slaney's scale) from 0 to sample_rate / 2, filter m = max(0, min(rising, falling)) scaled by
+    spaced in mel (Slaney's scale) from 0 to f_max (None: sample_rate / 2), filter m = max(0, min(rising, falling)) scaled by
     2 / (its upper edge - its lower edge, in Hz)."""
     sr, W, M = float(sample_rate), int(W), int(n_mels)
     if sr <= 0 or W < 2 or M < 1:
         raise SwcError(f"mel_filterbank: sample_rate={sample_rate!r}, W={W!r}, n_mels={n_mels!r}")
-    edges = _mel_to_hz(np.linspace(0.0, float(_hz_to_mel(sr / 2.0)), M + 2))
-    edges[0], edges[-1] = 0.0, sr / 2.0     # the end points are given, not the round trip through the mel scale
+    top = sr / 2.0 if f_max is None else float(f_max)
+    if not 0.0 < top <= sr / 2.0:
+        raise SwcError(f"mel_filterbank: f_max={f_max!r} (above 0, at most sample_rate / 2 = {sr / 2.0:g})")
+    edges = _mel_to_hz(np.linspace(0.0, float(_hz_to_mel(top)), M + 2))
+    edges[0], edges[-1] = 0.0, top          # the end points are given, not the round trip through the mel scale
     bins = np.arange(W // 2 + 1, dtype=np.float64) * (sr / W)
     rising = (bins[None, :] - edges[:M, None]) / (edges[1:M + 1] - edges[:M])[:, None]
     falling = (edges[2:, None] - bins[None, :]) / (edges[2:] - edges[1:M + 1])[:, None]
@@ -1022,3 +1031,201 @@ def dtw(feat_ref, feat_deg, band=0, device=torch.device("cuda")):
         counts = torch.tensor(tx + ty, dtype=torch.int32).to(device, non_blocking=True)
         r = ops.dtw(xf, yf, counts[:B], counts[B:], band=band, want=("total", "info", "mean", "path"))
     return {"mean": r["mean"], "total": r["total"], "steps": r["info"][:, 0], "path": r["path"]}
+
+
+# ---- a score after WARP-Q: subsequence DTW of patches of normalised cepstra (include/swc_subdtw.h) ----
+
+WARPQ_MELS = 40
+WARPQ_COEFFS = 13                                        # c0 .. c12
+WARPQ_F_MAX = 5000.0                                     # upper edge of the bank, in Hz (at most sample_rate / 2)
+WARPQ_STEPS = ((1, 1), (3, 2), (1, 3))                   # this project's default step set; any other goes through steps=
+ASYMMETRIC_STEPS = ((1, 0), (0, 3), (1, 3))              # a published variant without a diagonal step: see warpq()
+SYMMETRIC_STEPS = ops.SUBDTW_SYMMETRIC                   # (1, 1), (1, 0), (0, 1): the unconstrained steps of swc_dtw
+MAX_PATCH = _lib.SUBDTW_MAX_PATCH
+
+
+def warpq_params(sample_rate):
+    """-> (W, H): the smallest power of two >= 32 ms of samples, and 4 ms of samples (rounded)"""
+    try:
+        sr = int(sample_rate)
+    except (TypeError, ValueError):
+        raise SwcError(f"warpq: sample_rate={sample_rate!r}")
+    if sr < 1:
+        raise SwcError(f"warpq: sample_rate={sample_rate!r}")
+    W = 1 << max(int(math.ceil(0.032 * sr)) - 1, 0).bit_length()
+    H = max(int(round(0.004 * sr)), 1)
+    if W not in ops.CEPSTRA_WINDOWS or H > W:
+        raise SwcError(f"warpq: sample_rate={sr} gives a window of {W} samples and a hop of {H}: windows of {ops.CEPSTRA_WINDOWS} "
+                       "(include/swc_mcd.h)")
+    return W, H
+
+
+def warpq_patch(sample_rate, patch_ms):
+    """-> (Lp, Sp) of a swc_subdtw call: round(patch_ms / hop_ms) frames, every Lp // 2 frames.  SwcError outside 1 .. 256 frames"""
+    _, H = warpq_params(sample_rate)
+    try:
+        ms = float(patch_ms)
+    except (TypeError, ValueError):
+        raise SwcError(f"warpq: patch_ms={patch_ms!r}")
+    hop_ms = 1000.0 * H / int(sample_rate)
+    L = int(round(ms / hop_ms)) if 0.0 < ms < math.inf else 0
+    if not 1 <= L <= MAX_PATCH:
+        raise SwcError(f"warpq: patch_ms={patch_ms!r} is {L} frames of {hop_ms:g} ms: 1..{MAX_PATCH} (SWC_SUBDTW_MAX_PATCH of "
+                       "include/swc_subdtw.h)")
+    return L, max(L // 2, 1)
+
+
+def check_steps(who, steps):
+    """the step set of include/swc_subdtw.h as a tuple of (di, dj): 1 .. 4 distinct steps, 0 <= di, dj <= 3, di + dj >= 1, at
+    least one with di >= 1.  SwcError otherwise (the C side checks again)"""
+    try:
+        st = tuple((int(a), int(b)) for a, b in steps)
+    except (TypeError, ValueError):
+        raise SwcError(f"{who}: steps={steps!r}: pairs (di, dj)")
+    m = _lib.SUBDTW_MAX_STRIDE
+    if (not 1 <= len(st) <= _lib.SUBDTW_MAX_STEPS or len(set(st)) != len(st) or not any(a >= 1 for a, _ in st)
+            or any(not (0 <= a <= m and 0 <= b <= m and a + b >= 1) for a, b in st)):
+        raise SwcError(f"{who}: steps={steps!r}: 1..{_lib.SUBDTW_MAX_STEPS} distinct steps (di, dj) with 0 <= di, dj <= {m}, "
+                       "di + dj >= 1 and at least one di >= 1")
+    return st
+
+
+_WARPQ_TABLES = {}
+
+
+def warpq_table(sample_rate, device):
+    """The parameters and tables of warpq's swc_cepstra call at sample_rate on one device, built once and kept: W and H of
+    warpq_params, 40 Slaney filters from 0 to min(5 kHz, sample_rate / 2) (mel_filterbank with f_max, pack_filterbanks) and the
+    DCT rows 0 .. 12, built in float64 and rounded to f32 once: the `table` of ops.cepstra."""
+    def build(device):
+        W, H = warpq_params(sample_rate)
+        f_max = min(WARPQ_F_MAX, float(sample_rate) / 2.0)
+        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, WARPQ_MELS, f_max=f_max)])
+        t = {"W": W, "H": H, "n_mels": WARPQ_MELS, "K": WARPQ_COEFFS, "f_max": f_max, "sample_rate": int(sample_rate)}
+        for name, v in (("first", first), ("count", count), ("off", off), ("w", w),
+                        ("dct", dct_matrix(WARPQ_COEFFS, WARPQ_MELS, first=0).astype(np.float32))):
+            t[name] = torch.from_numpy(v).to(device)
+        return t
+    return _cached(_WARPQ_TABLES, sample_rate, device, build)
+
+
+def subsequence_dtw(query_feats, ref_feats, patch=None, step=None, steps=SYMMETRIC_STEPS, device=torch.device("cuda")):
+    """Subsequence DTW of caller-supplied features (swc_subdtw on any matrices): query_feats / ref_feats = lists of 2-D tensors
+    [T_i][D], one D <= 32 for all.  patch=None: every query (1 .. 256 frames) is matched as a whole against its reference, with
+    a free start and end there: "where in this recording does this snippet occur".  patch=L: every query is cut into patches
+    of L frames every `step` frames (default L // 2) and every patch is matched on its own.  steps: the step set (di, dj), di
+    frames of the query and dj frames of the reference; ties go to the step given first.  -> dict on `device`, per pair and
+    patch [B][P_max]: "cost" LongTensor (the summed distance along the path, in units of 2^(e - 17) of the features: see
+    include/swc_subdtw.h), "steps" (the cells of the path), "start", "end" (the first and last reference frame matched),
+    "status" IntTensor (0 ok, 1 nothing reachable, 2 the pair holds a NaN or Inf, 3 a whole query outside 1 .. 256 frames);
+    per pair: "score" DoubleTensor[B] (the median cost of the ok patches in the features' own unit, NaN without one) and
+    "patches" IntTensor[B][2] = ok, offered.  Nothing is synchronised."""
+    device = _pairs_on("subsequence_dtw", query_feats, ref_feats, _cuda("subsequence_dtw", "the search is a HIP kernel", device))
+    st = check_steps("subsequence_dtw", steps)
+    B = len(query_feats)
+    Lp = 0 if patch is None else int(patch)
+    if patch is not None and not 1 <= Lp <= MAX_PATCH:
+        raise SwcError(f"subsequence_dtw: patch={patch!r}: None, or 1..{MAX_PATCH} frames")
+    Sp = (max(Lp // 2, 1) if step is None else int(step))
+    if Sp < 1:
+        raise SwcError(f"subsequence_dtw: step={step!r} (>= 1)")
+    if B == 0:
+        z = lambda *shape, dtype=torch.int32: torch.zeros(shape, device=device, dtype=dtype)
+        return {"cost": z(0, 0, dtype=torch.int64), "steps": z(0, 0), "start": z(0, 0), "end": z(0, 0), "status": z(0, 0),
+                "score": z(0, dtype=torch.float64), "patches": z(0, 2)}
+    D = query_feats[0].shape[-1] if query_feats[0].dim() == 2 else -1
+    if any(f.dim() != 2 or f.shape[1] != D for f in list(query_feats) + list(ref_feats)) or not 1 <= D <= _lib.SUBDTW_MAX_D:
+        raise SwcError(f"subsequence_dtw: every feature matrix is [T][D] with one D in 1..{_lib.SUBDTW_MAX_D}")
+    tq, ty = [f.shape[0] for f in query_feats], [f.shape[0] for f in ref_feats]
+    if max(tq + ty) > MAX_FRAMES:
+        raise SwcError(f"subsequence_dtw: a matrix of {max(tq + ty)} frames: at most MAX_FRAMES = {MAX_FRAMES} "
+                       "(SWC_SUBDTW_MAX_FRAMES of include/swc_subdtw.h)")
+    with torch.cuda.device(device):
+        qf = torch.zeros((B, max(tq), D), device=device)
+        yf = torch.zeros((B, max(ty), D), device=device)
+        for b in range(B):
+            qf[b, :tq[b]] = query_feats[b].to(device=device, dtype=torch.float32)
+            yf[b, :ty[b]] = ref_feats[b].to(device=device, dtype=torch.float32)
+        counts = torch.tensor(tq + ty, dtype=torch.int32).to(device, non_blocking=True)
+        r = ops.subdtw(qf, yf, counts[:B], counts[B:], patch=Lp, step=Sp, steps=st)
+    i = r["info"]
+    return {"cost": r["cost"], "steps": i[..., 0], "start": i[..., 1], "end": i[..., 2], "status": i[..., 3], "score": r["score"],
+            "patches": r["patches"]}
+
+
+def _speech_only(who, rows, sample_rate, device):
+    """every row cut to the samples inside its speech_segments() runs, concatenated (an empty row where no speech is found): one
+    swc_activity call over the rows and one small read-back"""
+    rows, segs = _segments(who, rows, sample_rate, 15.9, 200, 50, 60, device)
+    out = []
+    for r, s in zip(rows, segs):
+        parts = [r[a:b] for a, b in s]
+        out.append(parts[0] if len(parts) == 1 else (torch.cat(parts) if parts else r[:0]))
+    return out
+
+
+def warpq(ref_list, deg_list, sample_rate=16000, patch_ms=400.0, steps=WARPQ_STEPS, vad=True, tracks=False, align=None,
+          max_lag_ms=50.0, fine=None, device=torch.device("cuda")):
+    """A full-reference score after WARP-Q (Jassim, Skoglund, Chinen and Hines, ICASSP 2021) for generative codecs, whose
+    output is plausible speech that is locally displaced and re-synthesised: pair i = (ref_list[i] clean, deg_list[i] degraded),
+    each row at its own length.  One swc_cepstra call over the 2 B rows (warpq_table: windows of 32 ms every 4 ms, 40 mel bands
+    up to 5 kHz, cepstral coefficients c0 .. c12), one swc_cmvn call (every coefficient of every row to zero mean and unit
+    variance) and one swc_subdtw call (include/swc_subdtw.h): the degraded row's cepstra are cut into patches of patch_ms every
+    half of that, every patch finds its best-matching stretch anywhere in the reference row by subsequence DTW under `steps`,
+    and the pair's value is the median of the patch costs.  It is the raw alignment cost in the normalised cepstra's unit, NOT
+    the paper's mapped MOS (which needs a trained mapper): lower is better, 0.0 means the two rows are identical.  There is no
+    lifter: the per-coefficient variance normalisation cancels any per-coefficient scale.  steps: pairs (di, dj) of degraded
+    and reference frames; the default (1, 1), (3, 2), (1, 3) is this project's choice, other published variants are passed here.
+    A set without a step that advances one frame on both sides, such as ASYMMETRIC_STEPS = (1, 0), (0, 3), (1, 3), cannot walk
+    the diagonal: under it even an identical pair has a positive score.
+    vad=True keeps, on each side independently, only the samples inside that row's speech_segments() runs, concatenated (one
+    small read-back, like trimmed()); a row with no speech gives an empty side and NaN.  vad=False adds no read-back.
+    -> dict on `device`: "warpq" DoubleTensor[B] (NaN without an ok patch), "patches" IntTensor[B][2] = ok, offered,
+    "frames_ref", "frames_deg" IntTensor[B]; with tracks=True also "cost" (per pair a DoubleTensor[P], NaN for a patch that is
+    not ok), "start", "end" (IntTensor[P]: the reference frames a patch was matched to): where a reconstruction fails.
+    align = "waveform" or "envelope": the pairs' constant delay is removed first (aligned(): one small read-back) and "lag"
+    IntTensor[B] added."""
+    state = {}
+
+    def check():
+        state["W"], state["H"] = warpq_params(sample_rate)
+        state["Lp"], state["Sp"] = warpq_patch(sample_rate, patch_ms)
+        state["steps"] = check_steps("warpq", steps)
+
+    def score(ref_list, deg_list, device):
+        B = len(ref_list)
+        if B == 0:
+            res = {"warpq": torch.zeros(0, device=device, dtype=torch.float64), "patches": torch.zeros((0, 2), device=device, dtype=torch.int32)}
+            res.update({k: torch.zeros(0, device=device, dtype=torch.int32) for k in ("frames_ref", "frames_deg")})
+            if tracks:
+                res.update(cost=[], start=[], end=[])
+            return res
+        H, Lp, Sp = state["H"], state["Lp"], state["Sp"]
+        table = warpq_table(sample_rate, device)
+        with torch.cuda.device(device):
+            x_rows, y_rows = _stage(ref_list, deg_list, device, cut=False)
+            rows = x_rows + y_rows
+            if vad:
+                rows = _speech_only("warpq", rows, sample_rate, device)
+            for r in rows:
+                if 1 + r.numel() // H > MAX_FRAMES:
+                    raise SwcError(f"warpq: a row of {r.numel()} samples is {1 + r.numel() // H} frames: at most MAX_FRAMES = {MAX_FRAMES} "
+                                   "(SWC_DTW_MAX_FRAMES of include/swc_mcd.h); score it in pieces")
+            c = ops.cepstra(rows, table, ldf=16)
+            ops.cmvn(c["cep"], c["frames"], WARPQ_COEFFS, out=c["cep"])
+            want = ("score", "patches") + (("cost", "info", "exps") if tracks else ())
+            r = ops.subdtw(c["cep"][B:], c["cep"][:B], c["frames"][B:], c["frames"][:B], D=WARPQ_COEFFS, patch=Lp, step=Sp,
+                           steps=state["steps"], want=want)
+            res = {"warpq": r["score"], "patches": r["patches"], "frames_ref": c["frames"][:B], "frames_deg": c["frames"][B:]}
+            if tracks:
+                ok = r["info"][..., 3] == _lib.SUBDTW_ST_OK
+                # 2^(e - 17) from its bit pattern: the one scaling of include/swc_subdtw.h, exact (torch.ldexp goes through pow)
+                scale = ((r["exps"].to(torch.int64) - (_lib.DTW_QBITS + 4) + 1023) << 52).view(torch.float64)
+                cost = r["cost"].to(torch.float64) * scale[:, None]
+                cost = torch.where(ok, cost, torch.full_like(cost, float("nan")))
+                P = [ops.subdtw_patches(t, Lp, Sp) for t in c["counts"][B:]]
+                res["cost"] = [cost[b, :P[b]] for b in range(B)]
+                res["start"] = [r["info"][b, :P[b], 1] for b in range(B)]
+                res["end"] = [r["info"][b, :P[b], 2] for b in range(B)]
+        return res
+    return _scored("warpq", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine, check=check)

@@ -1161,6 +1161,117 @@ def dtw(xf, yf, tx, ty, D=None, band=0, mode="warp", want=("total", "info", "mea
     return res
 
 
+SUBDTW_OUTPUTS = ("cost", "info", "score", "patches", "exps")
+SUBDTW_SYMMETRIC = ((1, 1), (1, 0), (0, 1))
+
+
+def cmvn(cep, frames, K, out=None, ldo=None):
+    """Every row's cepstra normalised to zero mean and unit variance per coefficient in one call (include/swc_subdtw.h swc_cmvn):
+    cep f32 [R][T_max][ldf] and frames int32 [R] as ops.cepstra returns them, K <= ldf the coefficients normalised.  -> f32
+    [R][T_max][ldo] (entries with t >= T of a row or k >= K are not written: the tensor comes from torch.zeros).  out = cep
+    normalises in place.  out, ldo (tests): the tensor to write and its row stride."""
+    lib = _lib.load()
+    _chk(cep, "cmvn cep", torch.float32)
+    _chk(frames, "cmvn frames", torch.int32)
+    if cep.dim() != 3 or not cep.is_contiguous():
+        raise _lib.SwcError("cmvn: cep is a contiguous [R][T_max][ldf] tensor")
+    R, t_max, ldf = cep.shape
+    K = int(K)
+    if R == 0 or frames.numel() != R or not frames.is_contiguous():
+        raise _lib.SwcError(f"cmvn: {R} rows and {frames.numel()} frame counts (one contiguous count per row, R >= 1)")
+    if not 1 <= K <= min(ldf, _lib.CEPSTRA_MAX_K):
+        raise _lib.SwcError(f"cmvn: K={K} (1..{min(ldf, _lib.CEPSTRA_MAX_K)})")
+    if out is None:
+        ldo = ldf if ldo is None else int(ldo)
+        out = torch.zeros((R, t_max, ldo), device=cep.device, dtype=torch.float32)
+    else:
+        _chk(out, "cmvn out", torch.float32)
+        ldo = (out.shape[-1] if out.dim() == 3 else -1) if ldo is None else int(ldo)
+        if ldo < K or out.numel() != R * t_max * ldo or not out.is_contiguous():
+            raise _lib.SwcError(f"cmvn: out is a contiguous tensor of {R} x {t_max} x ldo elements, ldo >= K")
+    _lib.check(lib.swc_cmvn(_ptr(cep), _ptr(frames), t_max, K, ldf, _ptr(out), ldo, R, _stream()), "swc_cmvn")
+    return out
+
+
+def subdtw_patches(t_q, patch, step):
+    """P of include/swc_subdtw.h for a query of t_q frames: patch = Lp (0: the whole query is the one patch), step = Sp"""
+    t_q, patch, step = int(t_q), int(patch), int(step)
+    if patch == 0:
+        return 1 if 1 <= t_q <= _lib.SUBDTW_MAX_PATCH else 0
+    return 0 if t_q < patch else 1 + (t_q - patch) // step
+
+
+def subdtw_workspace_layout(B, tmax_q, tmax_y, patch, step):
+    """the documented formula of swc_subdtw_workspace_bytes, part by part: -> ({name: (byte offset, bytes)}, total)"""
+    up = lambda v: (v + 255) // 256 * 256
+    p_max = 1 if patch == 0 else (0 if tmax_q < patch else 1 + (tmax_q - patch) // step)
+    parts, o = {}, 0
+    for name, size in (("peaks", 4 * B), ("qq", 64 * B * tmax_q), ("yq", 64 * B * tmax_y), ("cost", 8 * B * max(p_max, 1))):
+        parts[name] = (o, size)
+        o += up(size)
+    return parts, o
+
+
+def subdtw_workspace_bytes(B, tmax_q, tmax_y, patch, step):
+    """swc_subdtw_workspace_bytes of include/swc_subdtw.h"""
+    v = int(_lib.load().swc_subdtw_workspace_bytes(int(B), int(tmax_q), int(tmax_y), int(patch), int(step)))
+    if v < 0:
+        raise _lib.SwcError(f"subdtw: no workspace size for B={B}, Tmax_q={tmax_q}, Tmax_y={tmax_y}, patch={patch}, step={step}")
+    return v
+
+
+def subdtw(qf, yf, tq, ty, D=None, patch=0, step=1, steps=SUBDTW_SYMMETRIC, want=("cost", "info", "score", "patches"), ldp=None,
+           out=None, workspace=None):
+    """The subsequence DTW of every patch of every feature pair of a batch, and every pair's median, in one call
+    (include/swc_subdtw.h swc_subdtw): qf f32 [B][Tmax_q][ldf] (the side cut into patches), yf f32 [B][Tmax_y][ldf] (the side
+    searched) contiguous device tensors, tq / ty int32 [B] device tensors of frame counts, D <= ldf the features compared
+    (default ldf), patch = Lp (0: every pair's whole query is its one patch), step = Sp, steps = 1 .. 4 distinct (di, dj).
+    -> dict of the wanted outputs: cost int64 [B][ldp], info int32 [B][ldp][4] = N, start, end, status (entries of patches a
+    pair does not have are not written: the tensors come from torch.zeros), score float64 [B], patches int32 [B][2] = ok,
+    offered, exps int32 [B].  ldp, out, workspace (tests): the row stride of cost and info, a dict of output tensors to write
+    and a 256-byte aligned uint8 workspace to use instead."""
+    lib = _lib.load()
+    want = _want("subdtw", want, SUBDTW_OUTPUTS)
+    for name, t in (("qf", qf), ("yf", yf)):
+        _chk(t, f"subdtw {name}", torch.float32)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise _lib.SwcError(f"subdtw: {name} is a contiguous [B][Tmax][ldf] tensor")
+    B, tmax_q, ldf = qf.shape
+    if yf.shape[0] != B or yf.shape[2] != ldf or B == 0:
+        raise _lib.SwcError(f"subdtw: qf {tuple(qf.shape)} and yf {tuple(yf.shape)}: one non-zero B and one ldf expected")
+    tmax_y = yf.shape[1]
+    for name, t in (("tq", tq), ("ty", ty)):
+        _chk(t, f"subdtw {name}", torch.int32)
+        if t.numel() != B or not t.is_contiguous():
+            raise _lib.SwcError(f"subdtw: {name} holds one contiguous frame count per pair")
+    D = ldf if D is None else int(D)
+    patch, step = int(patch), int(step)
+    if not 1 <= D <= min(ldf, _lib.SUBDTW_MAX_D):
+        raise _lib.SwcError(f"subdtw: D={D} (1..{min(ldf, _lib.SUBDTW_MAX_D)})")
+    if not 0 <= patch <= _lib.SUBDTW_MAX_PATCH or step < 1:
+        raise _lib.SwcError(f"subdtw: patch={patch} (0..{_lib.SUBDTW_MAX_PATCH}), step={step} (>= 1)")
+    if max(tmax_q, tmax_y) > _lib.SUBDTW_MAX_FRAMES:
+        raise _lib.SwcError(f"subdtw: {tmax_q} and {tmax_y} frames: at most {_lib.SUBDTW_MAX_FRAMES} (include/swc_subdtw.h)")
+    try:
+        flat = [int(v) for s in steps for v in (s[0], s[1])]
+        bad = any(len(s) != 2 for s in steps) or not 1 <= len(flat) // 2 <= _lib.SUBDTW_MAX_STEPS
+    except (TypeError, ValueError, IndexError):
+        bad = True
+    if bad:
+        raise _lib.SwcError(f"subdtw: steps={steps!r}: 1..{_lib.SUBDTW_MAX_STEPS} pairs (di, dj)")
+    p_max = 1 if patch == 0 else subdtw_patches(tmax_q, patch, step)
+    ldp = max(p_max, 1) if ldp is None else int(ldp)    # (never an empty tensor: its address would be null)
+    workspace = _workspace("subdtw", subdtw_workspace_bytes(B, tmax_q, tmax_y, patch, step), workspace, qf.device)
+    shapes = {"cost": ((B, ldp), torch.int64), "info": ((B, ldp, _lib.SUBDTW_INFO), torch.int32), "score": ((B,), torch.float64),
+              "patches": ((B, 2), torch.int32), "exps": ((B,), torch.int32)}
+    res = _outputs("subdtw", {name: shapes[name] for name in want}, out, qf.device, torch.zeros)
+    arr = (C.c_int32 * len(flat))(*flat)
+    _lib.check(lib.swc_subdtw(_ptr(qf), _ptr(yf), _ptr(tq), _ptr(ty), tmax_q, tmax_y, D, ldf, patch, step, arr, len(flat) // 2,
+                              _ptr(res.get("cost")), _ptr(res.get("info")), ldp, _ptr(res.get("score")), _ptr(res.get("patches")),
+                              _ptr(res.get("exps")), _ptr(workspace), workspace.numel(), B, _stream()), "swc_subdtw")
+    return res
+
+
 LOUDNESS_VALUES = ("integrated", "range", "momentary_max", "short_term_max", "sample_peak", "true_peak", "blocks", "blocks_kept")
 
 
