@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 import yaml
 
-from . import bitstream, ops, packed, spec, trace
+from . import bitstream, metrics, ops, packed, spec, trace
 from ._lib import SwcError
 
 # precision presets: (encode-side GEMM operands, decode-side GEMM operands)
@@ -1520,6 +1520,28 @@ class AudioCodec(nn.Module):
                 out[order[k]] = wav[k - a, : n[k] * up]
         return {"syn_wav_list": out}
 
+    def _round_trip(self, who, what, wav_list, overlap_seconds, device):
+        """What the metric entry points below share: -> (the device to score on, the reconstruction of wav_list at
+        input_sample_rate: encode -> decode, resampled on the GPU when the output rate differs).  SwcError(`who`: `what` has
+        no CPU fallback) before anything runs when that device is not a GPU."""
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError(f"{who}: {what} (there is no CPU fallback)")
+        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
+        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
+        if self.output_sample_rate != self.input_sample_rate and len(syn):
+            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
+            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        return dev, syn
+
+    @staticmethod
+    def _both_sides(measure, wav_list, syn, keys, **kw):
+        """{"ref": measure(wav_list), "deg": measure(syn), "<k>_diff": deg - ref for k in keys}"""
+        res = {"ref": measure(wav_list, **kw), "deg": measure(syn, **kw)}
+        for k in keys:
+            res[k + "_diff"] = res["deg"][k] - res["ref"][k]
+        return res
+
     @_on_model_device
     @torch.inference_mode()
     def stoi(self, wav_list, overlap_seconds=10, device=torch.device("cuda")):
@@ -1527,15 +1549,7 @@ class AudioCodec(nn.Module):
         (waveforms at input_sample_rate; the reconstruction is resampled on the GPU when the output rate differs).
         -> (d FloatTensor[B], segs IntTensor[B]) on the model's device: utterance i's STOI and the number of segments it
         averages (segs 0 and d 1e-5 for an utterance too short to score)."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("stoi: the metric is a HIP kernel (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("stoi", "the metric is a HIP kernel", wav_list, overlap_seconds, device)
         return metrics.stoi(wav_list, syn, sample_rate=self.input_sample_rate, device=dev)
 
     @_on_model_device
@@ -1544,15 +1558,7 @@ class AudioCodec(nn.Module):
         """stoi() with the two measures beside it: encode -> decode -> metrics.quality of the reconstruction against the input.
         -> dict on the model's device: "stoi", "estoi" (FloatTensor[B]), "si_sdr" (FloatTensor[B], dB) and "segs"
         (IntTensor[B]); "stoi" and "segs" are what stoi() returns."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("quality: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("quality", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.quality(wav_list, syn, sample_rate=self.input_sample_rate, device=dev)
 
     @_on_model_device
@@ -1561,15 +1567,7 @@ class AudioCodec(nn.Module):
         """quality() for the magnitude-domain distances: encode -> decode -> metrics.spectral of the reconstruction against
         the input.  -> dict on the model's device: "mel", "stft", "lsd" (FloatTensor[B] each, as wanted), "parts"
         (FloatTensor[B][7][4]) and "scales"."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("spectral: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("spectral", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.spectral(wav_list, syn, sample_rate=self.input_sample_rate, device=dev, want=want)
 
     @_on_model_device
@@ -1579,15 +1577,7 @@ class AudioCodec(nn.Module):
         """spectral() for the LPC-domain and segmental measures: encode -> decode -> metrics.segmental of the reconstruction
         against the input.  -> dict on the model's device: "llr", "is", "cd", "segsnr", "fwsegsnr" (DoubleTensor[B] each, as
         wanted), "frames", "frames_lpc", "frames_fw" (IntTensor[B]) and, with tracks, "track"."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("segmental: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("segmental", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.segmental(wav_list, syn, sample_rate=self.input_sample_rate, device=dev, want=want, tracks=tracks)
 
     @_on_model_device
@@ -1596,15 +1586,7 @@ class AudioCodec(nn.Module):
         """quality() for the pitch measures: encode -> decode -> metrics.pitch of the reconstruction against the input.
         -> dict on the model's device: "f0_rmse_cents", "f0_corr", "gpe", "vde", "vuv_f1", "voiced_ref", "voiced_deg"
         (FloatTensor[B] each), "frames" (IntTensor[B]) and, with tracks, "tracks_ref" / "tracks_deg"."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("pitch: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("pitch", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.pitch(wav_list, syn, sample_rate=self.input_sample_rate, f_min=f_min, f_max=f_max, device=dev, tracks=tracks)
 
     @_on_model_device
@@ -1613,21 +1595,9 @@ class AudioCodec(nn.Module):
         """quality() for the loudness numbers: encode -> decode -> metrics.loudness of the input and of the reconstruction (at
         input_sample_rate).  -> dict on the model's device: "ref" and "deg", each the dict of metrics.loudness, and
         "integrated_diff", "range_diff", "true_peak_db_diff" (deg - ref, float64 [B]; NaN where either side is)."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("loudness: the meter is a HIP kernel (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
-        ref = metrics.loudness(wav_list, sample_rate=self.input_sample_rate, device=dev)
-        deg = metrics.loudness(syn, sample_rate=self.input_sample_rate, device=dev)
-        res = {"ref": ref, "deg": deg}
-        for k in ("integrated", "range", "true_peak_db"):
-            res[k + "_diff"] = deg[k] - ref[k]
-        return res
+        dev, syn = self._round_trip("loudness", "the meter is a HIP kernel", wav_list, overlap_seconds, device)
+        return self._both_sides(metrics.loudness, wav_list, syn, ("integrated", "range", "true_peak_db"), sample_rate=self.input_sample_rate,
+                                device=dev)
 
     @_on_model_device
     @torch.inference_mode()
@@ -1635,21 +1605,9 @@ class AudioCodec(nn.Module):
         """quality() for the speech levels: encode -> decode -> metrics.active_level of the input and of the reconstruction (at
         input_sample_rate).  -> dict on the model's device: "ref" and "deg", each the dict of metrics.active_level, and
         "active_level_db_diff", "long_term_db_diff", "activity_diff" (deg - ref, float64 [B]; NaN where either side is)."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("active_level: the activity detector is a HIP kernel (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
-        ref = metrics.active_level(wav_list, sample_rate=self.input_sample_rate, device=dev)
-        deg = metrics.active_level(syn, sample_rate=self.input_sample_rate, device=dev)
-        res = {"ref": ref, "deg": deg}
-        for k in ("active_level_db", "long_term_db", "activity"):
-            res[k + "_diff"] = deg[k] - ref[k]
-        return res
+        dev, syn = self._round_trip("active_level", "the activity detector is a HIP kernel", wav_list, overlap_seconds, device)
+        return self._both_sides(metrics.active_level, wav_list, syn, ("active_level_db", "long_term_db", "activity"),
+                                sample_rate=self.input_sample_rate, device=dev)
 
     @_on_model_device
     @torch.inference_mode()
@@ -1657,15 +1615,7 @@ class AudioCodec(nn.Module):
         """quality() for the mel-cepstral distortion: encode -> decode -> metrics.mcd of the reconstruction against the input.
         -> dict on the model's device: "mcd" (FloatTensor[B], dB), "frames_ref", "frames_deg", "steps" (IntTensor[B]) and,
         with path, "path"."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("mcd: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("mcd", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.mcd(wav_list, syn, sample_rate=self.input_sample_rate, dtw=dtw, band_ms=band_ms, path=path, device=dev)
 
     @_on_model_device
@@ -1674,15 +1624,7 @@ class AudioCodec(nn.Module):
         """quality() for the score after WARP-Q: encode -> decode -> metrics.warpq of the reconstruction against the input.
         -> dict on the model's device: "warpq" (DoubleTensor[B], lower is better), "patches" (IntTensor[B][2] = ok, offered),
         "frames_ref", "frames_deg" (IntTensor[B]) and, with tracks, "cost", "start", "end" per patch."""
-        from . import metrics
-        dev = self._resolve_device(device)
-        if dev.type != "cuda":
-            raise SwcError("warpq: the metrics are HIP kernels (there is no CPU fallback)")
-        codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device)["codes_list"]
-        syn = self.decode(codes, overlap_seconds=overlap_seconds, device=device)["syn_wav_list"]
-        if self.output_sample_rate != self.input_sample_rate and len(syn):
-            y, n_out = ops.resample([w.reshape(-1).contiguous() for w in syn], self.output_sample_rate, self.input_sample_rate)
-            syn = [y[k, : n_out[k]] for k in range(len(syn))]
+        dev, syn = self._round_trip("warpq", "the metrics are HIP kernels", wav_list, overlap_seconds, device)
         return metrics.warpq(wav_list, syn, sample_rate=self.input_sample_rate, patch_ms=patch_ms,
                              steps=metrics.WARPQ_STEPS if steps is None else steps, vad=vad, tracks=tracks, device=dev)
 

@@ -93,16 +93,27 @@ def stoi_taps(sample_rate):
     return torch.from_numpy(K.astype(np.float32)), orig, new, width
 
 
-def _cached(cache, sample_rate, device, build):
-    """cache[(rate, device)], from build(device) the first time: a table is built once per rate and device, and kept"""
-    device = torch.device(device)
-    key = (int(sample_rate), device.type, device.index)
-    if key not in cache:
-        cache[key] = build(device)
-    return cache[key]
-
-
 _TABLES = {}
+
+
+def _cached(kind, sample_rate, device, build):
+    """_TABLES[(kind, rate, device)], from build(device) the first time: a table is built once per kind, rate and device, and kept"""
+    device = torch.device(device)
+    key = (kind, int(sample_rate), device.type, device.index)
+    if key not in _TABLES:
+        _TABLES[key] = build(device)
+    return _TABLES[key]
+
+
+def _with_banks(t, banks, device, dct=None):
+    """the table t (host numbers) with the device tensors of a front end added: "first", "count", "off", "w" = the dense float64
+    `banks` packed (pack_filterbanks) and, where given, "dct" rounded to f32 once"""
+    arrays = dict(zip(("first", "count", "off", "w"), pack_filterbanks(banks)))
+    if dct is not None:
+        arrays["dct"] = dct.astype(np.float32)
+    for name, v in arrays.items():
+        t[name] = torch.from_numpy(v).to(device)
+    return t
 
 
 def stoi_table(sample_rate, device):
@@ -116,7 +127,7 @@ def stoi_table(sample_rate, device):
             raise SwcError(f"stoi: sample_rate={sample_rate}: the 10 kHz filter ({orig}:{new}, {t['run']} taps per phase) needs {floats} "
                            f"f32 words of LDS per resampler tile, {RESAMPLE_MAX_LDS_FLOATS} fit; convert to one of {RATES} first")
         return t
-    return _cached(_TABLES, sample_rate, device, build)
+    return _cached("stoi", sample_rate, device, build)
 
 
 def stoi(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
@@ -162,11 +173,16 @@ def _cuda(who, what, device):
     return device
 
 
+def _indexed(device):
+    """a GPU (_cuda) with its index filled in: the current device's, which is the first CUDA call of a metric"""
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 def _pairs_on(who, ref_list, deg_list, device):
-    """the pair-count check, then (the first CUDA call of a metric) the device with its index filled in"""
+    """the pair-count check, then the device with its index filled in"""
     if len(deg_list) != len(ref_list):
         raise SwcError(f"{who}: {len(ref_list)} reference and {len(deg_list)} degraded waveforms")
-    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+    return _indexed(device)
 
 
 def _scored(who, what, score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine=None, check=None):
@@ -282,21 +298,15 @@ def pack_filterbanks(banks):
     return i32(first), i32(count), i32(off), (np.concatenate(w) if w else np.zeros(0, np.float32))
 
 
-_SPECTRAL_TABLES = {}
-
-
 def spectral_table(sample_rate, device):
     """The fixed scale list (windows 32 .. 2048 with 5 .. 320 mel filters, all flagged MEL; STFT on 512 and 2048; LSD on
     2048) and its packed mel banks at sample_rate on one device, built once and kept: the `table` of ops.spectral."""
     def build(device):
         flags = [_lib.SPECTRAL_MEL | (_lib.SPECTRAL_STFT if w in SPECTRAL_STFT_WINDOWS else 0) | (_lib.SPECTRAL_LSD if w == SPECTRAL_LSD_WINDOW else 0)
                  for w in SPECTRAL_WINDOWS]
-        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, M) for W, M in zip(SPECTRAL_WINDOWS, SPECTRAL_MELS)])
         t = {"win": list(SPECTRAL_WINDOWS), "n_mels": list(SPECTRAL_MELS), "flags": flags, "sample_rate": int(sample_rate)}
-        for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
-            t[name] = torch.from_numpy(v).to(device)
-        return t
-    return _cached(_SPECTRAL_TABLES, sample_rate, device, build)
+        return _with_banks(t, [mel_filterbank(sample_rate, W, M) for W, M in zip(SPECTRAL_WINDOWS, SPECTRAL_MELS)], device)
+    return _cached("spectral", sample_rate, device, build)
 
 
 def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), want=ops.SPECTRAL_METRICS, align=None, max_lag_ms=50.0, fine=None,
@@ -347,19 +357,23 @@ def spectral(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"),
                    check=lambda: ops._want("spectral", want, ops.SPECTRAL_METRICS))
 
 
+def _spectral_one(key, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine):
+    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=(key,), align=align, max_lag_ms=max_lag_ms, fine=fine)[key]
+
+
 def mel_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the multi-scale mel distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("mel",), align=align, max_lag_ms=max_lag_ms, fine=fine)["mel"]
+    return _spectral_one("mel", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
 def stft_distance(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the multi-resolution STFT distance alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("stft",), align=align, max_lag_ms=max_lag_ms, fine=fine)["stft"]
+    return _spectral_one("stft", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
 def lsd(ref_list, deg_list, sample_rate=16000, device=torch.device("cuda"), align=None, max_lag_ms=50.0, fine=None):
     """the log-spectral distance (W = 2048) alone: -> FloatTensor[B] (NaN for an empty pair)"""
-    return spectral(ref_list, deg_list, sample_rate=sample_rate, device=device, want=("lsd",), align=align, max_lag_ms=max_lag_ms, fine=fine)["lsd"]
+    return _spectral_one("lsd", ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine)
 
 
 # ---- pitch (include/swc_pitch.h) ----
@@ -413,8 +427,7 @@ def f0(wav_list, sample_rate=16000, f_min=62.5, f_max=500.0, device=torch.device
     params = ops.pitch_params(sample_rate, f_min, f_max)
     if len(wav_list) == 0:
         return []
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _indexed(device)
     with torch.cuda.device(device):
         x_rows, _ = _stage(wav_list, wav_list, device)
         return _tracks(ops.pitch(x_rows, None, params, want=("f0_x",)), "x")
@@ -598,8 +611,7 @@ def _rows(wav_list, device):
 
 def _loudness_device(who, sample_rate, device):
     ops.loudness_check_rate(sample_rate)
-    device = _cuda(who, "the meter is a HIP kernel", device)
-    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+    return _indexed(_cuda(who, "the meter is a HIP kernel", device))
 
 
 def loudness(wav_list, sample_rate=16000, device=torch.device("cuda"), want=LOUDNESS_KEYS):
@@ -623,6 +635,17 @@ def loudness(wav_list, sample_rate=16000, device=torch.device("cuda"), want=LOUD
     return {w: cols[w] for w in want}
 
 
+def _normalised(wav_list, device, normalise):
+    """head and tail of normalised() and level_normalised(): the rows staged, normalise(rows) -> (out [B][cols], gains, flags)
+    on them, and row i's own length of out as its view"""
+    if len(wav_list) == 0:
+        return [], torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        rows = _rows(wav_list, device)
+        out, gains, flags = normalise(rows)
+    return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+
+
 def normalised(wav_list, sample_rate, target_lufs=-23.0, true_peak_db=-1.0, device=torch.device("cuda")):
     """Every waveform of a list brought to target_lufs integrated loudness, with a gain small enough to keep its true peak under
     true_peak_db: one swc_loudness and one swc_loudness_normalise call, the gain computed on the device (no read-back, nothing
@@ -630,12 +653,7 @@ def normalised(wav_list, sample_rate, target_lufs=-23.0, true_peak_db=-1.0, devi
     FloatTensor[B] (linear); flags IntTensor[B], bit 0 = the row has no integrated loudness and is passed through with gain 1,
     bit 1 = the true-peak ceiling set the gain."""
     device = _loudness_device("normalised", sample_rate, device)
-    if len(wav_list) == 0:
-        return [], torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
-    with torch.cuda.device(device):
-        rows = _rows(wav_list, device)
-        out, gains, flags = ops.loudness_normalise(rows, ops.loudness(rows, sample_rate), target_lufs, true_peak_db)
-    return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+    return _normalised(wav_list, device, lambda rows: ops.loudness_normalise(rows, ops.loudness(rows, sample_rate), target_lufs, true_peak_db))
 
 
 def level_matched(ref_list, deg_list, sample_rate, device=torch.device("cuda")):
@@ -667,8 +685,7 @@ ACTIVE_LEVEL_KEYS = ("active_level_db", "long_term_db", "activity", "threshold_d
 
 def _activity_device(who, sample_rate, device):
     ops.activity_check_rate(sample_rate)
-    device = _cuda(who, "the activity detector is a HIP kernel", device)
-    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+    return _indexed(_cuda(who, "the activity detector is a HIP kernel", device))
 
 
 def active_level(wav_list, sample_rate=16000, margin_db=15.9, hangover_ms=200, device=torch.device("cuda")):
@@ -783,13 +800,8 @@ def level_normalised(wav_list, sample_rate, target_dbov=-26.0, margin_db=15.9, h
     flags): rows = views of ONE zero-padded batch, row i of its waveform's length; gains FloatTensor[B] (linear); flags
     IntTensor[B], bit 0 = the row has no active level and is passed through with gain 1, bit 1 = the peak set the gain."""
     device = _activity_device("level_normalised", sample_rate, device)
-    if len(wav_list) == 0:
-        return [], torch.zeros(0, device=device), torch.zeros(0, device=device, dtype=torch.int32)
-    with torch.cuda.device(device):
-        rows = _rows(wav_list, device)
-        values = ops.activity(rows, sample_rate, margin_db, hangover_ms / 1000.0)["values"]
-        out, gains, flags = ops.activity_normalise(rows, values, target_dbov)
-    return [out[i, :r.numel()] for i, r in enumerate(rows)], gains, flags
+    return _normalised(wav_list, device, lambda rows: ops.activity_normalise(
+        rows, ops.activity(rows, sample_rate, margin_db, hangover_ms / 1000.0)["values"], target_dbov))
 
 
 # ---- LPC-domain and segmental measures (include/swc_segmental.h) ----
@@ -814,20 +826,14 @@ def segmental_params(sample_rate):
     return W, (10 if sr < 10000 else 16)
 
 
-_SEGMENTAL_TABLES = {}
-
-
 def segmental_table(sample_rate, device):
     """The bands of fwSegSNR at sample_rate on one device, built once and kept: 25 Slaney mel triangles over 0 .. fs / 2 on the
     bins of segmental_params' window (mel_filterbank, pack_filterbanks): the `table` of ops.segmental"""
     def build(device):
         W, P = segmental_params(sample_rate)
-        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, SEGMENTAL_BANDS)])
         t = {"W": W, "P": P, "K": SEGMENTAL_BANDS, "sample_rate": int(sample_rate)}
-        for name, v in (("first", first), ("count", count), ("off", off), ("w", w)):
-            t[name] = torch.from_numpy(v).to(device)
-        return t
-    return _cached(_SEGMENTAL_TABLES, sample_rate, device, build)
+        return _with_banks(t, [mel_filterbank(sample_rate, W, SEGMENTAL_BANDS)], device)
+    return _cached("segmental", sample_rate, device, build)
 
 
 def segmental(ref_list, deg_list, sample_rate=16000, want=SEGMENTAL_KEYS, tracks=False, align=None, max_lag_ms=50.0, fine=None,
@@ -907,17 +913,40 @@ MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)          # mean cepstral distanc
 MAX_FRAMES = _lib.DTW_MAX_FRAMES
 
 
-def mcd_params(sample_rate):
-    """-> (W, H): the smallest power of two >= 25 ms of samples, and 10 ms of samples (rounded)"""
+def _window_hop(who, sample_rate, window_s, hop_s):
+    """-> (W, H) of a swc_cepstra call: the smallest power of two >= window_s of samples, and hop_s of samples (rounded)"""
     sr = int(sample_rate)
     if sr < 1:
-        raise SwcError(f"mcd: sample_rate={sample_rate!r}")
-    W = 1 << max(int(math.ceil(0.025 * sr)) - 1, 0).bit_length()
-    H = max(int(round(0.010 * sr)), 1)
+        raise SwcError(f"{who}: sample_rate={sample_rate!r}")
+    W = 1 << max(int(math.ceil(window_s * sr)) - 1, 0).bit_length()
+    H = max(int(round(hop_s * sr)), 1)
     if W not in ops.CEPSTRA_WINDOWS or H > W:
-        raise SwcError(f"mcd: sample_rate={sr} gives a window of {W} samples and a hop of {H}: windows of {ops.CEPSTRA_WINDOWS} "
+        raise SwcError(f"{who}: sample_rate={sr} gives a window of {W} samples and a hop of {H}: windows of {ops.CEPSTRA_WINDOWS} "
                        "(include/swc_mcd.h)")
     return W, H
+
+
+def _hops(who, name, ms, sample_rate, H):
+    """`ms` milliseconds in hops of H samples -> (ms as a float, one hop in ms, round(ms / hop), 0 unless 0 < ms < inf)"""
+    try:
+        ms = float(ms)
+    except (TypeError, ValueError):
+        raise SwcError(f"{who}: {name}={ms!r}")
+    hop_ms = 1000.0 * H / int(sample_rate)
+    return ms, hop_ms, (int(round(ms / hop_ms)) if 0.0 < ms < math.inf else 0)
+
+
+def _check_frames(who, rows, H):
+    """SwcError for a row whose cepstra at hop H would be more than MAX_FRAMES frames"""
+    for r in rows:
+        if 1 + r.numel() // H > MAX_FRAMES:
+            raise SwcError(f"{who}: a row of {r.numel()} samples is {1 + r.numel() // H} frames: at most MAX_FRAMES = {MAX_FRAMES} "
+                           "(SWC_DTW_MAX_FRAMES of include/swc_mcd.h); score it in pieces")
+
+
+def mcd_params(sample_rate):
+    """-> (W, H): the smallest power of two >= 25 ms of samples, and 10 ms of samples (rounded)"""
+    return _window_hop("mcd", sample_rate, 0.025, 0.010)
 
 
 def dct_matrix(n_coeffs, n_mels, first=1):
@@ -930,37 +959,25 @@ def dct_matrix(n_coeffs, n_mels, first=1):
     return d
 
 
-_MCD_TABLES = {}
-
-
 def mcd_table(sample_rate, device):
     """The parameters and tables of a swc_cepstra call at sample_rate on one device, built once and kept: W and H of
     mcd_params, 80 Slaney filters (mel_filterbank, pack_filterbanks) and the DCT rows 1 .. 13, built in float64 and rounded to
     f32 once: the `table` of ops.cepstra."""
     def build(device):
         W, H = mcd_params(sample_rate)
-        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, MCD_MELS)])
         t = {"W": W, "H": H, "n_mels": MCD_MELS, "K": MCD_COEFFS, "sample_rate": int(sample_rate)}
-        for name, v in (("first", first), ("count", count), ("off", off), ("w", w),
-                        ("dct", dct_matrix(MCD_COEFFS, MCD_MELS).astype(np.float32))):
-            t[name] = torch.from_numpy(v).to(device)
-        return t
-    return _cached(_MCD_TABLES, sample_rate, device, build)
+        return _with_banks(t, [mel_filterbank(sample_rate, W, MCD_MELS)], device, dct=dct_matrix(MCD_COEFFS, MCD_MELS))
+    return _cached("mcd", sample_rate, device, build)
 
 
 def mcd_band(sample_rate, band_ms):
     """r of a swc_dtw call: round(band_ms / hop_ms), 0 (no band) for None.  SwcError below one hop"""
     if band_ms is None:
         return 0
-    _, H = mcd_params(sample_rate)
-    try:
-        ms = float(band_ms)
-    except (TypeError, ValueError):
-        raise SwcError(f"mcd: band_ms={band_ms!r}")
-    hop_ms = 1000.0 * H / int(sample_rate)
+    ms, hop_ms, r = _hops("mcd", "band_ms", band_ms, sample_rate, mcd_params(sample_rate)[1])
     if not (hop_ms <= ms < math.inf):
         raise SwcError(f"mcd: band_ms={band_ms!r}: None, or at least one hop ({hop_ms:g} ms)")
-    return int(round(ms / hop_ms))
+    return r
 
 
 def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=False, align=None, max_lag_ms=50.0, fine=None,
@@ -980,10 +997,7 @@ def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=Fals
     def check():
         W, H = mcd_params(sample_rate)
         state["band"] = mcd_band(sample_rate, band_ms)
-        for r in list(ref_list) + list(deg_list):
-            if 1 + r.numel() // H > MAX_FRAMES:
-                raise SwcError(f"mcd: a row of {r.numel()} samples is {1 + r.numel() // H} frames: at most MAX_FRAMES = {MAX_FRAMES} "
-                               "(SWC_DTW_MAX_FRAMES of include/swc_mcd.h); score it in pieces")
+        _check_frames("mcd", list(ref_list) + list(deg_list), H)
 
     def score(ref_list, deg_list, device):
         B = len(ref_list)
@@ -1006,6 +1020,26 @@ def mcd(ref_list, deg_list, sample_rate=16000, dtw=True, band_ms=None, path=Fals
     return _scored("mcd", "the metrics are HIP kernels", score, ref_list, deg_list, sample_rate, device, align, max_lag_ms, fine, check=check)
 
 
+def _stage_features(who, feat_x, feat_y, device, max_d, limit):
+    """The feature matrices of dtw() and subsequence_dtw(): every one [T][D] with one D in 1 .. max_d and at most MAX_FRAMES
+    frames (`limit` names the header's constant), else SwcError before any CUDA call.  -> (xf, yf zero-padded f32
+    [B][T_max][D] on `device`, one row copied at a time, and counts int32 [2 B]: the frames of x, then of y, in ONE upload)"""
+    B = len(feat_x)
+    D = feat_x[0].shape[-1] if feat_x[0].dim() == 2 else -1
+    if any(f.dim() != 2 or f.shape[1] != D for f in list(feat_x) + list(feat_y)) or not 1 <= D <= max_d:
+        raise SwcError(f"{who}: every feature matrix is [T][D] with one D in 1..{max_d}")
+    tx, ty = [f.shape[0] for f in feat_x], [f.shape[0] for f in feat_y]
+    if max(tx + ty) > MAX_FRAMES:
+        raise SwcError(f"{who}: a matrix of {max(tx + ty)} frames: at most MAX_FRAMES = {MAX_FRAMES} ({limit})")
+    with torch.cuda.device(device):
+        xf = torch.zeros((B, max(tx), D), device=device)
+        yf = torch.zeros((B, max(ty), D), device=device)
+        for b in range(B):
+            xf[b, :tx[b]] = feat_x[b].to(device=device, dtype=torch.float32)
+            yf[b, :ty[b]] = feat_y[b].to(device=device, dtype=torch.float32)
+        return xf, yf, torch.tensor(tx + ty, dtype=torch.int32).to(device, non_blocking=True)
+
+
 def dtw(feat_ref, feat_deg, band=0, device=torch.device("cuda")):
     """Exact DTW of caller-supplied features (swc_dtw on any matrices): feat_ref / feat_deg = lists of 2-D tensors [T_i][D], one
     D <= 32 for all.  -> dict on `device`: "mean" FloatTensor[B] (the mean Euclidean distance per path step, after the
@@ -1016,19 +1050,8 @@ def dtw(feat_ref, feat_deg, band=0, device=torch.device("cuda")):
     if B == 0:
         return {"mean": torch.zeros(0, device=device), "total": torch.zeros(0, device=device, dtype=torch.int64),
                 "steps": torch.zeros(0, device=device, dtype=torch.int32), "path": torch.zeros((0, 0, 2), device=device, dtype=torch.int32)}
-    D = feat_ref[0].shape[-1] if feat_ref[0].dim() == 2 else -1
-    if any(f.dim() != 2 or f.shape[1] != D for f in list(feat_ref) + list(feat_deg)) or not 1 <= D <= _lib.DTW_MAX_D:
-        raise SwcError(f"dtw: every feature matrix is [T][D] with one D in 1..{_lib.DTW_MAX_D}")
-    tx, ty = [f.shape[0] for f in feat_ref], [f.shape[0] for f in feat_deg]
-    if max(tx + ty) > MAX_FRAMES:
-        raise SwcError(f"dtw: a matrix of {max(tx + ty)} frames: at most MAX_FRAMES = {MAX_FRAMES} (SWC_DTW_MAX_FRAMES of include/swc_mcd.h)")
+    xf, yf, counts = _stage_features("dtw", feat_ref, feat_deg, device, _lib.DTW_MAX_D, "SWC_DTW_MAX_FRAMES of include/swc_mcd.h")
     with torch.cuda.device(device):
-        xf = torch.zeros((B, max(tx), D), device=device)
-        yf = torch.zeros((B, max(ty), D), device=device)
-        for b in range(B):
-            xf[b, :tx[b]] = feat_ref[b].to(device=device, dtype=torch.float32)
-            yf[b, :ty[b]] = feat_deg[b].to(device=device, dtype=torch.float32)
-        counts = torch.tensor(tx + ty, dtype=torch.int32).to(device, non_blocking=True)
         r = ops.dtw(xf, yf, counts[:B], counts[B:], band=band, want=("total", "info", "mean", "path"))
     return {"mean": r["mean"], "total": r["total"], "steps": r["info"][:, 0], "path": r["path"]}
 
@@ -1047,28 +1070,14 @@ MAX_PATCH = _lib.SUBDTW_MAX_PATCH
 def warpq_params(sample_rate):
     """-> (W, H): the smallest power of two >= 32 ms of samples, and 4 ms of samples (rounded)"""
     try:
-        sr = int(sample_rate)
-    except (TypeError, ValueError):
+        return _window_hop("warpq", sample_rate, 0.032, 0.004)
+    except (TypeError, ValueError):         # a rate that is no number is refused by name here; mcd_params lets the error through
         raise SwcError(f"warpq: sample_rate={sample_rate!r}")
-    if sr < 1:
-        raise SwcError(f"warpq: sample_rate={sample_rate!r}")
-    W = 1 << max(int(math.ceil(0.032 * sr)) - 1, 0).bit_length()
-    H = max(int(round(0.004 * sr)), 1)
-    if W not in ops.CEPSTRA_WINDOWS or H > W:
-        raise SwcError(f"warpq: sample_rate={sr} gives a window of {W} samples and a hop of {H}: windows of {ops.CEPSTRA_WINDOWS} "
-                       "(include/swc_mcd.h)")
-    return W, H
 
 
 def warpq_patch(sample_rate, patch_ms):
     """-> (Lp, Sp) of a swc_subdtw call: round(patch_ms / hop_ms) frames, every Lp // 2 frames.  SwcError outside 1 .. 256 frames"""
-    _, H = warpq_params(sample_rate)
-    try:
-        ms = float(patch_ms)
-    except (TypeError, ValueError):
-        raise SwcError(f"warpq: patch_ms={patch_ms!r}")
-    hop_ms = 1000.0 * H / int(sample_rate)
-    L = int(round(ms / hop_ms)) if 0.0 < ms < math.inf else 0
+    _, hop_ms, L = _hops("warpq", "patch_ms", patch_ms, sample_rate, warpq_params(sample_rate)[1])
     if not 1 <= L <= MAX_PATCH:
         raise SwcError(f"warpq: patch_ms={patch_ms!r} is {L} frames of {hop_ms:g} ms: 1..{MAX_PATCH} (SWC_SUBDTW_MAX_PATCH of "
                        "include/swc_subdtw.h)")
@@ -1090,9 +1099,6 @@ def check_steps(who, steps):
     return st
 
 
-_WARPQ_TABLES = {}
-
-
 def warpq_table(sample_rate, device):
     """The parameters and tables of warpq's swc_cepstra call at sample_rate on one device, built once and kept: W and H of
     warpq_params, 40 Slaney filters from 0 to min(5 kHz, sample_rate / 2) (mel_filterbank with f_max, pack_filterbanks) and the
@@ -1100,13 +1106,9 @@ def warpq_table(sample_rate, device):
     def build(device):
         W, H = warpq_params(sample_rate)
         f_max = min(WARPQ_F_MAX, float(sample_rate) / 2.0)
-        first, count, off, w = pack_filterbanks([mel_filterbank(sample_rate, W, WARPQ_MELS, f_max=f_max)])
         t = {"W": W, "H": H, "n_mels": WARPQ_MELS, "K": WARPQ_COEFFS, "f_max": f_max, "sample_rate": int(sample_rate)}
-        for name, v in (("first", first), ("count", count), ("off", off), ("w", w),
-                        ("dct", dct_matrix(WARPQ_COEFFS, WARPQ_MELS, first=0).astype(np.float32))):
-            t[name] = torch.from_numpy(v).to(device)
-        return t
-    return _cached(_WARPQ_TABLES, sample_rate, device, build)
+        return _with_banks(t, [mel_filterbank(sample_rate, W, WARPQ_MELS, f_max=f_max)], device, dct=dct_matrix(WARPQ_COEFFS, WARPQ_MELS, first=0))
+    return _cached("warpq", sample_rate, device, build)
 
 
 def subsequence_dtw(query_feats, ref_feats, patch=None, step=None, steps=SYMMETRIC_STEPS, device=torch.device("cuda")):
@@ -1133,20 +1135,9 @@ def subsequence_dtw(query_feats, ref_feats, patch=None, step=None, steps=SYMMETR
         z = lambda *shape, dtype=torch.int32: torch.zeros(shape, device=device, dtype=dtype)
         return {"cost": z(0, 0, dtype=torch.int64), "steps": z(0, 0), "start": z(0, 0), "end": z(0, 0), "status": z(0, 0),
                 "score": z(0, dtype=torch.float64), "patches": z(0, 2)}
-    D = query_feats[0].shape[-1] if query_feats[0].dim() == 2 else -1
-    if any(f.dim() != 2 or f.shape[1] != D for f in list(query_feats) + list(ref_feats)) or not 1 <= D <= _lib.SUBDTW_MAX_D:
-        raise SwcError(f"subsequence_dtw: every feature matrix is [T][D] with one D in 1..{_lib.SUBDTW_MAX_D}")
-    tq, ty = [f.shape[0] for f in query_feats], [f.shape[0] for f in ref_feats]
-    if max(tq + ty) > MAX_FRAMES:
-        raise SwcError(f"subsequence_dtw: a matrix of {max(tq + ty)} frames: at most MAX_FRAMES = {MAX_FRAMES} "
-                       "(SWC_SUBDTW_MAX_FRAMES of include/swc_subdtw.h)")
+    qf, yf, counts = _stage_features("subsequence_dtw", query_feats, ref_feats, device, _lib.SUBDTW_MAX_D,
+                                     "SWC_SUBDTW_MAX_FRAMES of include/swc_subdtw.h")
     with torch.cuda.device(device):
-        qf = torch.zeros((B, max(tq), D), device=device)
-        yf = torch.zeros((B, max(ty), D), device=device)
-        for b in range(B):
-            qf[b, :tq[b]] = query_feats[b].to(device=device, dtype=torch.float32)
-            yf[b, :ty[b]] = ref_feats[b].to(device=device, dtype=torch.float32)
-        counts = torch.tensor(tq + ty, dtype=torch.int32).to(device, non_blocking=True)
         r = ops.subdtw(qf, yf, counts[:B], counts[B:], patch=Lp, step=Sp, steps=st)
     i = r["info"]
     return {"cost": r["cost"], "steps": i[..., 0], "start": i[..., 1], "end": i[..., 2], "status": i[..., 3], "score": r["score"],
@@ -1207,10 +1198,7 @@ def warpq(ref_list, deg_list, sample_rate=16000, patch_ms=400.0, steps=WARPQ_STE
             rows = x_rows + y_rows
             if vad:
                 rows = _speech_only("warpq", rows, sample_rate, device)
-            for r in rows:
-                if 1 + r.numel() // H > MAX_FRAMES:
-                    raise SwcError(f"warpq: a row of {r.numel()} samples is {1 + r.numel() // H} frames: at most MAX_FRAMES = {MAX_FRAMES} "
-                                   "(SWC_DTW_MAX_FRAMES of include/swc_mcd.h); score it in pieces")
+            _check_frames("warpq", rows, H)
             c = ops.cepstra(rows, table, ldf=16)
             ops.cmvn(c["cep"], c["frames"], WARPQ_COEFFS, out=c["cep"])
             want = ("score", "patches") + (("cost", "info", "exps") if tracks else ())

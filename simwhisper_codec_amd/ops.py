@@ -48,7 +48,8 @@ def _chk(t, name, dtype=None):
     return t
 
 
-# ---- what the five metric calls (stoi, quality, spectral, pitch, align) share: DESIGN.md "Metric calls: the shared path" ----
+# ---- what the metric calls (stoi, quality, spectral, pitch, align, lag_track / warp, cepstra / dtw, cmvn / subdtw, loudness,
+# activity, segmental and the two normalise calls) share: DESIGN.md "Metric calls: the shared path" ----
 
 def _pair_rows(who, x_rows, y_rows, *, equal_lengths, y_optional=False):
     """The row checks of a metric call: equal, non-zero counts; every row a contiguous 1-D f32 tensor on the current device;
@@ -113,6 +114,90 @@ def _want(who, want, choices, may_be_empty=False):
     if any(w not in choices for w in want) or len(set(want)) != len(want) or not (want or may_be_empty):
         raise _lib.SwcError(f"{who}: want={want!r}: a {'' if may_be_empty else 'non-empty '}choice of {choices}")
     return want
+
+
+def _workspace_bytes(v, who, what, *shown):
+    """v = what a swc_<who>_workspace_bytes returned -> bytes.  Where the library has no size (a negative value): SwcError naming
+    `what` filled with the arguments `shown`; the message is built only then"""
+    if v < 0:
+        raise _lib.SwcError(f"{who}: no workspace size for " + what.format(*shown))
+    return int(v)
+
+
+def _check_rate(who, sample_rate, lo, hi, multiple):
+    """fs of a swc_loudness or swc_activity call as an int: an integer (of any type) in lo .. hi that `multiple` divides"""
+    try:
+        fs = int(sample_rate)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"{who}: sample_rate={sample_rate!r}")
+    if fs != sample_rate or not lo <= fs <= hi or fs % multiple:
+        kind = "an integer" if multiple == 1 else f"a multiple of {multiple}"
+        raise _lib.SwcError(f"{who}: sample_rate={sample_rate!r}: {kind} in {lo}..{hi} (include/swc_{who}.h)")
+    return fs
+
+
+def _bank_table(who, table, n, per):
+    """A packed bank table (metrics.pack_filterbanks on the device): "first", "count", "off" int32 with `n` entries each (one
+    per `per`, as the message says) and the weights "w" f32, every one contiguous and on the current device"""
+    for name in ("first", "count", "off"):
+        _chk(table[name], f"{who} table {name}", torch.int32)
+        if table[name].numel() != n or not table[name].is_contiguous():
+            raise _lib.SwcError(f"{who}: table {name} holds one contiguous entry per {per}")
+    _chk(table["w"], f"{who} table w", torch.float32)
+    if not table["w"].is_contiguous():
+        raise _lib.SwcError(f"{who}: the table's weights are contiguous")
+
+
+def _feature_pair(who, x_name, xf, yf, tx, ty, D):
+    """The tensor checks of dtw and subdtw: `x_name` ("xf" / "qf") and "yf" contiguous f32 [B][Tmax][ldf] with one non-zero B
+    and one ldf, the frame counts contiguous int32 [B], all on the current device; D defaults to ldf.
+    -> (B, Tmax of x, Tmax of y, ldf, D)"""
+    for name, t in ((x_name, xf), ("yf", yf)):
+        _chk(t, f"{who} {name}", torch.float32)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise _lib.SwcError(f"{who}: {name} is a contiguous [B][Tmax][ldf] tensor")
+    B, tmax_x, ldf = xf.shape
+    if yf.shape[0] != B or yf.shape[2] != ldf or B == 0:
+        raise _lib.SwcError(f"{who}: {x_name} {tuple(xf.shape)} and yf {tuple(yf.shape)}: one non-zero B and one ldf expected")
+    for name, t in (("t" + x_name[0], tx), ("ty", ty)):
+        _chk(t, f"{who} {name}", torch.int32)
+        if t.numel() != B or not t.is_contiguous():
+            raise _lib.SwcError(f"{who}: {name} holds one contiguous frame count per pair")
+    return B, tmax_x, yf.shape[1], ldf, (ldf if D is None else int(D))
+
+
+def _normalise(who, n_values, x_rows, values, scalars, cols, out):
+    """The body of loudness_normalise and activity_normalise (swc_<who>): the row checks; `scalars` = {name: value}, finite
+    numbers; `values` float64 [B][n_values] as the measuring call left it on the device; out f32 [B][cols] from torch (cols
+    defaults to the longest row) or the caller's view with unit column stride.  -> (out, gains f32 [B], flags int32 [B])"""
+    lib = _lib.load()
+    n_in, _, device = _pair_rows(who, x_rows, None, equal_lengths=False, y_optional=True)
+    B = len(n_in)
+    def refuse(why=""):
+        return _lib.SwcError(f"{who}: " + ", ".join(f"{k}={v!r}" for k, v in scalars.items()) + why)
+    try:
+        nums = [float(v) for v in scalars.values()]
+    except (TypeError, ValueError):
+        raise refuse()
+    if not all(abs(v) <= 1e3 for v in nums):
+        raise refuse(": finite numbers" if len(nums) > 1 else ": a finite number")
+    _chk(values, f"{who} values", torch.float64)
+    if values.numel() != B * n_values or not values.is_contiguous():
+        raise _lib.SwcError(f"{who}: values is a contiguous tensor of {B} x {n_values} elements")
+    if out is None:
+        cols = max(n_in) if cols is None else int(cols)
+        out = torch.empty((B, cols), device=device, dtype=torch.float32)
+    else:
+        _chk(out, f"{who} out", torch.float32)
+        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
+            raise _lib.SwcError(f"{who}: out must be [B, cols] with unit column stride")
+        cols = out.shape[1]
+    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
+    res = _outputs(who, {"gains": ((B,), torch.float32), "flags": ((B,), torch.int32)}, None, device, torch.empty)
+    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
+    _lib.check(getattr(lib, "swc_" + who)(_ptr(xp), _ptr(n), _ptr(values), *nums, _ptr(out), ld, cols, _ptr(res["gains"]),
+                                          _ptr(res["flags"]), B, _stream()), "swc_" + who)
+    return out, res["gains"], res["flags"]
 
 
 def _gemm_args(A, W, M, N, K, *, out=None, out_dtype=None, lda=None, ldw=None, ldc=None, bias=None, gamma=None,
@@ -613,10 +698,8 @@ def flac_encode(rows, rate, blocksize=4096, md5=True, max_n=None, out=None, work
 
 def stoi_workspace_bytes(B, max_n_in, orig, new):
     """swc_stoi_workspace_bytes of include/swc_metrics.h"""
-    v = int(_lib.load().swc_stoi_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))
-    if v < 0:
-        raise _lib.SwcError(f"stoi: no workspace size for B={B}, max_n_in={max_n_in}, rates {orig}:{new}")
-    return v
+    return _workspace_bytes(_lib.load().swc_stoi_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)),
+                            "stoi", "B={}, max_n_in={}, rates {}:{}", B, max_n_in, orig, new)
 
 
 def stoi_workspace_layout(B, max_n_in, orig, new):
@@ -657,10 +740,8 @@ def stoi(x_rows, y_rows, table, max_n_in=None, d=None, segs=None, workspace=None
 
 def quality_workspace_bytes(B, max_n_in, orig, new):
     """swc_quality_workspace_bytes of include/swc_quality.h"""
-    v = int(_lib.load().swc_quality_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)))
-    if v < 0:
-        raise _lib.SwcError(f"quality: no workspace size for B={B}, max_n_in={max_n_in}, rates {orig}:{new}")
-    return v
+    return _workspace_bytes(_lib.load().swc_quality_workspace_bytes(int(B), int(max_n_in), int(orig), int(new)), "quality",
+                            "B={}, max_n_in={}, rates {}:{}", B, max_n_in, orig, new)
 
 
 def quality_workspace_layout(B, max_n_in, orig, new):
@@ -725,10 +806,8 @@ def _spectral_windows(win):
 def spectral_workspace_bytes(B, max_n_in, win):
     """swc_spectral_workspace_bytes of include/swc_spectral.h; win = the windows of the scale list"""
     win, arr = _spectral_windows(win)
-    v = int(_lib.load().swc_spectral_workspace_bytes(int(B), int(max_n_in), arr, len(win)))
-    if v < 0:
-        raise _lib.SwcError(f"spectral: no workspace size for B={B}, max_n_in={max_n_in}, windows {win}")
-    return v
+    return _workspace_bytes(_lib.load().swc_spectral_workspace_bytes(int(B), int(max_n_in), arr, len(win)),
+                            "spectral", "B={}, max_n_in={}, windows {}", B, max_n_in, win)
 
 
 def spectral_workspace_layout(B, max_n_in, win):
@@ -765,13 +844,7 @@ def spectral(x_rows, y_rows, table, want=SPECTRAL_METRICS, parts=True, max_n_in=
     if len(table["n_mels"]) != S or len(table["flags"]) != S:
         raise _lib.SwcError("spectral: win, n_mels and flags are lists of one length")
     c_mels, c_flags = (C.c_int32 * max(S, 1))(*table["n_mels"]), (C.c_int32 * max(S, 1))(*table["flags"])
-    for name in ("first", "count", "off"):
-        _chk(table[name], f"spectral table {name}", torch.int32)
-        if table[name].numel() != sum(table["n_mels"]) or not table[name].is_contiguous():
-            raise _lib.SwcError(f"spectral: table {name} holds one contiguous entry per filter of every scale")
-    _chk(table["w"], "spectral table w", torch.float32)
-    if not table["w"].is_contiguous():
-        raise _lib.SwcError("spectral: the table's weights are contiguous")
+    _bank_table("spectral", table, sum(table["n_mels"]), "filter of every scale")
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
     workspace = _workspace("spectral", spectral_workspace_bytes(B, max_n, win), workspace, device)
     specs = {name: ((B,), torch.float32) for name in want}
@@ -812,10 +885,8 @@ def pitch_frames(n, params):
 
 def pitch_workspace_bytes(B, max_n_in, params):
     """swc_pitch_workspace_bytes of include/swc_pitch.h"""
-    v = int(_lib.load().swc_pitch_workspace_bytes(int(B), int(max_n_in), int(params["W"]), int(params["tau_max"]), int(params["H"])))
-    if v < 0:
-        raise _lib.SwcError(f"pitch: no workspace size for B={B}, max_n_in={max_n_in}, {params}")
-    return v
+    v = _lib.load().swc_pitch_workspace_bytes(int(B), int(max_n_in), int(params["W"]), int(params["tau_max"]), int(params["H"]))
+    return _workspace_bytes(v, "pitch", "B={}, max_n_in={}, {}", B, max_n_in, params)
 
 
 def pitch(x_rows, y_rows, params, want=PITCH_OUTPUTS, max_n_in=None, ldt=None, out=None, workspace=None):
@@ -853,10 +924,8 @@ ALIGN_MODES = {"waveform": _lib.ALIGN_WAVEFORM, "envelope": _lib.ALIGN_ENVELOPE}
 
 def align_workspace_bytes(B, max_nx, max_ny, L):
     """swc_align_workspace_bytes of include/swc_align.h"""
-    v = int(_lib.load().swc_align_workspace_bytes(int(B), int(max_nx), int(max_ny), int(L)))
-    if v < 0:
-        raise _lib.SwcError(f"align: no workspace size for B={B}, max_nx={max_nx}, max_ny={max_ny}, L={L}")
-    return v
+    return _workspace_bytes(_lib.load().swc_align_workspace_bytes(int(B), int(max_nx), int(max_ny), int(L)),
+                            "align", "B={}, max_nx={}, max_ny={}, L={}", B, max_nx, max_ny, L)
 
 
 def align(x_rows, y_rows, L, mode, want=("info", "values"), max_nx=None, max_ny=None, ldc=None, out=None, workspace=None):
@@ -936,11 +1005,9 @@ def track_segments(n, S, H):
 
 def lag_track_workspace_bytes(B, max_nx, max_ny, S, H, Rs):
     """swc_lag_track_workspace_bytes of include/swc_track.h"""
-    v = int(_lib.load().swc_lag_track_workspace_bytes(int(B), int(max_nx), int(max_ny), int(S), int(H), int(Rs)))
-    if v < 0:
-        raise _lib.SwcError(f"lag_track: no workspace size for B={B}, max_nx={max_nx}, max_ny={max_ny}, S={S}, H={H}, Rs={Rs} "
-                            f"(Rs <= {_lib.TRACK_MAX_RANGE}, rows <= {_lib.TRACK_MAX_N}, at most {_lib.TRACK_MAX_SEGMENTS} segments)")
-    return v
+    v = _lib.load().swc_lag_track_workspace_bytes(int(B), int(max_nx), int(max_ny), int(S), int(H), int(Rs))
+    return _workspace_bytes(v, "lag_track", "B={}, max_nx={}, max_ny={}, S={}, H={}, Rs={} (Rs <= {}, rows <= {}, at most {} segments)",
+                            B, max_nx, max_ny, S, H, Rs, _lib.TRACK_MAX_RANGE, _lib.TRACK_MAX_N, _lib.TRACK_MAX_SEGMENTS)
 
 
 def _d0_column(who, d0, B):
@@ -1073,10 +1140,8 @@ def cepstra_frames(n, H):
 
 def cepstra_workspace_bytes(R, max_n_in, W, H):
     """swc_cepstra_workspace_bytes of include/swc_mcd.h (0: the call keeps every intermediate in LDS)"""
-    v = int(_lib.load().swc_cepstra_workspace_bytes(int(R), int(max_n_in), int(W), int(H)))
-    if v < 0:
-        raise _lib.SwcError(f"cepstra: no workspace size for R={R}, max_n_in={max_n_in}, W={W}, H={H}")
-    return v
+    return _workspace_bytes(_lib.load().swc_cepstra_workspace_bytes(int(R), int(max_n_in), int(W), int(H)),
+                            "cepstra", "R={}, max_n_in={}, W={}, H={}", R, max_n_in, W, H)
 
 
 def cepstra(rows, table, max_n_in=None, ldf=None, out=None, workspace=None):
@@ -1091,13 +1156,9 @@ def cepstra(rows, table, max_n_in=None, ldf=None, out=None, workspace=None):
     n_in, _, device = _pair_rows("cepstra", rows, None, equal_lengths=False, y_optional=True)
     R = len(n_in)
     W, H, M, K = (int(table[k]) for k in ("W", "H", "n_mels", "K"))
-    for name in ("first", "count", "off"):
-        _chk(table[name], f"cepstra table {name}", torch.int32)
-        if table[name].numel() != M or not table[name].is_contiguous():
-            raise _lib.SwcError(f"cepstra: table {name} holds one contiguous entry per filter")
-    _chk(table["w"], "cepstra table w", torch.float32)
+    _bank_table("cepstra", table, M, "filter")
     _chk(table["dct"], "cepstra table dct", torch.float32)
-    if not table["w"].is_contiguous() or not table["dct"].is_contiguous() or table["dct"].numel() != K * M:
+    if not table["dct"].is_contiguous() or table["dct"].numel() != K * M:
         raise _lib.SwcError("cepstra: the table's weights are contiguous, and dct holds K x n_mels entries")
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
     ldf = K if ldf is None else int(ldf)
@@ -1114,10 +1175,8 @@ def cepstra(rows, table, max_n_in=None, ldf=None, out=None, workspace=None):
 
 def dtw_workspace_bytes(B, tmax_x, tmax_y, with_path):
     """swc_dtw_workspace_bytes of include/swc_mcd.h"""
-    v = int(_lib.load().swc_dtw_workspace_bytes(int(B), int(tmax_x), int(tmax_y), int(bool(with_path))))
-    if v < 0:
-        raise _lib.SwcError(f"dtw: no workspace size for B={B}, Tmax_x={tmax_x}, Tmax_y={tmax_y}")
-    return v
+    return _workspace_bytes(_lib.load().swc_dtw_workspace_bytes(int(B), int(tmax_x), int(tmax_y), int(bool(with_path))), "dtw",
+                            "B={}, Tmax_x={}, Tmax_y={}", B, tmax_x, tmax_y)
 
 
 def dtw(xf, yf, tx, ty, D=None, band=0, mode="warp", want=("total", "info", "mean"), ldp=None, out=None, workspace=None):
@@ -1131,19 +1190,7 @@ def dtw(xf, yf, tx, ty, D=None, band=0, mode="warp", want=("total", "info", "mea
     want = _want("dtw", want, DTW_OUTPUTS)
     if mode not in DTW_MODES:
         raise _lib.SwcError(f"dtw: mode={mode!r}: one of {tuple(DTW_MODES)}")
-    for name, t in (("xf", xf), ("yf", yf)):
-        _chk(t, f"dtw {name}", torch.float32)
-        if t.dim() != 3 or not t.is_contiguous():
-            raise _lib.SwcError(f"dtw: {name} is a contiguous [B][Tmax][ldf] tensor")
-    B, tmax_x, ldf = xf.shape
-    if yf.shape[0] != B or yf.shape[2] != ldf or B == 0:
-        raise _lib.SwcError(f"dtw: xf {tuple(xf.shape)} and yf {tuple(yf.shape)}: one non-zero B and one ldf expected")
-    tmax_y = yf.shape[1]
-    for name, t in (("tx", tx), ("ty", ty)):
-        _chk(t, f"dtw {name}", torch.int32)
-        if t.numel() != B or not t.is_contiguous():
-            raise _lib.SwcError(f"dtw: {name} holds one contiguous frame count per pair")
-    D = ldf if D is None else int(D)
+    B, tmax_x, tmax_y, ldf, D = _feature_pair("dtw", "xf", xf, yf, tx, ty, D)
     band = int(band)
     if not (1 <= D <= min(ldf, _lib.DTW_MAX_D)) or band < 0:
         raise _lib.SwcError(f"dtw: D={D} (1..{min(ldf, _lib.DTW_MAX_D)}), band={band} (>= 0)")
@@ -1214,10 +1261,8 @@ def subdtw_workspace_layout(B, tmax_q, tmax_y, patch, step):
 
 def subdtw_workspace_bytes(B, tmax_q, tmax_y, patch, step):
     """swc_subdtw_workspace_bytes of include/swc_subdtw.h"""
-    v = int(_lib.load().swc_subdtw_workspace_bytes(int(B), int(tmax_q), int(tmax_y), int(patch), int(step)))
-    if v < 0:
-        raise _lib.SwcError(f"subdtw: no workspace size for B={B}, Tmax_q={tmax_q}, Tmax_y={tmax_y}, patch={patch}, step={step}")
-    return v
+    return _workspace_bytes(_lib.load().swc_subdtw_workspace_bytes(int(B), int(tmax_q), int(tmax_y), int(patch), int(step)), "subdtw",
+                            "B={}, Tmax_q={}, Tmax_y={}, patch={}, step={}", B, tmax_q, tmax_y, patch, step)
 
 
 def subdtw(qf, yf, tq, ty, D=None, patch=0, step=1, steps=SUBDTW_SYMMETRIC, want=("cost", "info", "score", "patches"), ldp=None,
@@ -1232,19 +1277,7 @@ def subdtw(qf, yf, tq, ty, D=None, patch=0, step=1, steps=SUBDTW_SYMMETRIC, want
     and a 256-byte aligned uint8 workspace to use instead."""
     lib = _lib.load()
     want = _want("subdtw", want, SUBDTW_OUTPUTS)
-    for name, t in (("qf", qf), ("yf", yf)):
-        _chk(t, f"subdtw {name}", torch.float32)
-        if t.dim() != 3 or not t.is_contiguous():
-            raise _lib.SwcError(f"subdtw: {name} is a contiguous [B][Tmax][ldf] tensor")
-    B, tmax_q, ldf = qf.shape
-    if yf.shape[0] != B or yf.shape[2] != ldf or B == 0:
-        raise _lib.SwcError(f"subdtw: qf {tuple(qf.shape)} and yf {tuple(yf.shape)}: one non-zero B and one ldf expected")
-    tmax_y = yf.shape[1]
-    for name, t in (("tq", tq), ("ty", ty)):
-        _chk(t, f"subdtw {name}", torch.int32)
-        if t.numel() != B or not t.is_contiguous():
-            raise _lib.SwcError(f"subdtw: {name} holds one contiguous frame count per pair")
-    D = ldf if D is None else int(D)
+    B, tmax_q, tmax_y, ldf, D = _feature_pair("subdtw", "qf", qf, yf, tq, ty, D)
     patch, step = int(patch), int(step)
     if not 1 <= D <= min(ldf, _lib.SUBDTW_MAX_D):
         raise _lib.SwcError(f"subdtw: D={D} (1..{min(ldf, _lib.SUBDTW_MAX_D)})")
@@ -1277,14 +1310,7 @@ LOUDNESS_VALUES = ("integrated", "range", "momentary_max", "short_term_max", "sa
 
 def loudness_check_rate(sample_rate):
     """fs of a swc_loudness call: a multiple of 10 in 8000 .. 48000 (include/swc_loudness.h), SwcError otherwise"""
-    try:
-        fs = int(sample_rate)
-    except (TypeError, ValueError):
-        raise _lib.SwcError(f"loudness: sample_rate={sample_rate!r}")
-    if fs != sample_rate or not _lib.LOUDNESS_MIN_FS <= fs <= _lib.LOUDNESS_MAX_FS or fs % 10:
-        raise _lib.SwcError(f"loudness: sample_rate={sample_rate!r}: a multiple of 10 in {_lib.LOUDNESS_MIN_FS}..{_lib.LOUDNESS_MAX_FS} "
-                            "(include/swc_loudness.h)")
-    return fs
+    return _check_rate("loudness", sample_rate, _lib.LOUDNESS_MIN_FS, _lib.LOUDNESS_MAX_FS, 10)
 
 
 def loudness_coefficients(sample_rate):
@@ -1299,10 +1325,8 @@ def loudness_coefficients(sample_rate):
 
 def loudness_workspace_bytes(B, max_n_in, sample_rate):
     """swc_loudness_workspace_bytes of include/swc_loudness.h"""
-    v = int(_lib.load().swc_loudness_workspace_bytes(int(B), int(max_n_in), int(sample_rate)))
-    if v < 0:
-        raise _lib.SwcError(f"loudness: no workspace size for B={B}, max_n_in={max_n_in}, sample_rate={sample_rate}")
-    return v
+    return _workspace_bytes(_lib.load().swc_loudness_workspace_bytes(int(B), int(max_n_in), int(sample_rate)), "loudness",
+                            "B={}, max_n_in={}, sample_rate={}", B, max_n_in, sample_rate)
 
 
 def loudness(x_rows, sample_rate, max_n_in=None, out=None, workspace=None):
@@ -1334,32 +1358,8 @@ def loudness_normalise(x_rows, values, target_lufs=-23.0, true_peak_db=-1.0, col
     scaled samples and zeros behind them, gains f32 [B], flags int32 [B]: bit 0 = not measured (the gain is 1), bit 1 = the
     ceiling set the gain).  cols defaults to the longest row; a longer row is cut.  `out` (tests): an f32 device view [B, cols]
     with unit column stride to write into instead."""
-    lib = _lib.load()
-    n_in, _, device = _pair_rows("loudness_normalise", x_rows, None, equal_lengths=False, y_optional=True)
-    B = len(n_in)
-    try:
-        target, ceiling = float(target_lufs), float(true_peak_db)
-    except (TypeError, ValueError):
-        raise _lib.SwcError(f"loudness_normalise: target_lufs={target_lufs!r}, true_peak_db={true_peak_db!r}")
-    if not (abs(target) <= 1e3 and abs(ceiling) <= 1e3):
-        raise _lib.SwcError(f"loudness_normalise: target_lufs={target_lufs!r}, true_peak_db={true_peak_db!r}: finite numbers")
-    _chk(values, "loudness_normalise values", torch.float64)
-    if values.numel() != B * _lib.LOUDNESS_VALUES or not values.is_contiguous():
-        raise _lib.SwcError(f"loudness_normalise: values is a contiguous tensor of {B} x {_lib.LOUDNESS_VALUES} elements")
-    if out is None:
-        cols = max(n_in) if cols is None else int(cols)
-        out = torch.empty((B, cols), device=device, dtype=torch.float32)
-    else:
-        _chk(out, "loudness_normalise out", torch.float32)
-        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
-            raise _lib.SwcError("loudness_normalise: out must be [B, cols] with unit column stride")
-        cols = out.shape[1]
-    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
-    res = _outputs("loudness_normalise", {"gains": ((B,), torch.float32), "flags": ((B,), torch.int32)}, None, device, torch.empty)
-    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
-    _lib.check(lib.swc_loudness_normalise(_ptr(xp), _ptr(n), _ptr(values), target, ceiling, _ptr(out), ld, cols, _ptr(res["gains"]),
-                                          _ptr(res["flags"]), B, _stream()), "swc_loudness_normalise")
-    return out, res["gains"], res["flags"]
+    return _normalise("loudness_normalise", _lib.LOUDNESS_VALUES, x_rows, values, {"target_lufs": target_lufs, "true_peak_db": true_peak_db},
+                      cols, out)
 
 
 ACTIVITY_VALUES = ("active_level", "long_term", "activity", "threshold", "sample_peak", "active_samples", "runs", "crossing")
@@ -1367,14 +1367,7 @@ ACTIVITY_VALUES = ("active_level", "long_term", "activity", "threshold", "sample
 
 def activity_check_rate(sample_rate):
     """fs of a swc_activity call: an integer in 8000 .. 48000 (include/swc_activity.h), SwcError otherwise"""
-    try:
-        fs = int(sample_rate)
-    except (TypeError, ValueError):
-        raise _lib.SwcError(f"activity: sample_rate={sample_rate!r}")
-    if fs != sample_rate or not _lib.ACTIVITY_MIN_FS <= fs <= _lib.ACTIVITY_MAX_FS:
-        raise _lib.SwcError(f"activity: sample_rate={sample_rate!r}: an integer in {_lib.ACTIVITY_MIN_FS}..{_lib.ACTIVITY_MAX_FS} "
-                            "(include/swc_activity.h)")
-    return fs
+    return _check_rate("activity", sample_rate, _lib.ACTIVITY_MIN_FS, _lib.ACTIVITY_MAX_FS, 1)
 
 
 def activity_coefficients(sample_rate, hangover_s=0.2):
@@ -1391,10 +1384,8 @@ def activity_coefficients(sample_rate, hangover_s=0.2):
 
 def activity_workspace_bytes(B, max_n_in, sample_rate):
     """swc_activity_workspace_bytes of include/swc_activity.h"""
-    v = int(_lib.load().swc_activity_workspace_bytes(int(B), int(max_n_in), int(sample_rate)))
-    if v < 0:
-        raise _lib.SwcError(f"activity: no workspace size for B={B}, max_n_in={max_n_in}, sample_rate={sample_rate}")
-    return v
+    return _workspace_bytes(_lib.load().swc_activity_workspace_bytes(int(B), int(max_n_in), int(sample_rate)), "activity",
+                            "B={}, max_n_in={}, sample_rate={}", B, max_n_in, sample_rate)
 
 
 def activity_run_capacity(max_n_in, hangover):
@@ -1440,32 +1431,7 @@ def activity_normalise(x_rows, values, target_db=-26.0, cols=None, out=None):
     swc_activity_normalise).  -> (out f32 [B][cols]: row b holds its scaled samples and zeros behind them, gains f32 [B], flags
     int32 [B]: bit 0 = not measured (the gain is 1), bit 1 = the peak set the gain).  cols defaults to the longest row; a
     longer row is cut.  `out` (tests): an f32 device view [B, cols] with unit column stride to write into instead."""
-    lib = _lib.load()
-    n_in, _, device = _pair_rows("activity_normalise", x_rows, None, equal_lengths=False, y_optional=True)
-    B = len(n_in)
-    try:
-        target = float(target_db)
-    except (TypeError, ValueError):
-        raise _lib.SwcError(f"activity_normalise: target_db={target_db!r}")
-    if not abs(target) <= 1e3:
-        raise _lib.SwcError(f"activity_normalise: target_db={target_db!r}: a finite number")
-    _chk(values, "activity_normalise values", torch.float64)
-    if values.numel() != B * _lib.ACTIVITY_VALUES or not values.is_contiguous():
-        raise _lib.SwcError(f"activity_normalise: values is a contiguous tensor of {B} x {_lib.ACTIVITY_VALUES} elements")
-    if out is None:
-        cols = max(n_in) if cols is None else int(cols)
-        out = torch.empty((B, cols), device=device, dtype=torch.float32)
-    else:
-        _chk(out, "activity_normalise out", torch.float32)
-        if out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1]):
-            raise _lib.SwcError("activity_normalise: out must be [B, cols] with unit column stride")
-        cols = out.shape[1]
-    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
-    res = _outputs("activity_normalise", {"gains": ((B,), torch.float32), "flags": ((B,), torch.int32)}, None, device, torch.empty)
-    xp, n = _row_table(device, [r.data_ptr() for r in x_rows], n_in)
-    _lib.check(lib.swc_activity_normalise(_ptr(xp), _ptr(n), _ptr(values), target, _ptr(out), ld, cols, _ptr(res["gains"]),
-                                          _ptr(res["flags"]), B, _stream()), "swc_activity_normalise")
-    return out, res["gains"], res["flags"]
+    return _normalise("activity_normalise", _lib.ACTIVITY_VALUES, x_rows, values, {"target_db": target_db}, cols, out)
 
 
 SEGMENTAL_VALUES = ("llr", "is", "cd", "segsnr", "fwsegsnr", "frames", "frames_lpc", "frames_fw")
@@ -1491,10 +1457,8 @@ def _segmental_params(W, P, K):
 def segmental_workspace_bytes(B, max_n_in, W, P, K=0):
     """swc_segmental_workspace_bytes of include/swc_segmental.h"""
     W, P, K = _segmental_params(W, P, K)
-    v = int(_lib.load().swc_segmental_workspace_bytes(int(B), int(max_n_in), W, P, K))
-    if v < 0:
-        raise _lib.SwcError(f"segmental: no workspace size for B={B}, max_n_in={max_n_in}, W={W}, P={P}, K={K}")
-    return v
+    return _workspace_bytes(_lib.load().swc_segmental_workspace_bytes(int(B), int(max_n_in), W, P, K),
+                            "segmental", "B={}, max_n_in={}, W={}, P={}, K={}", B, max_n_in, W, P, K)
 
 
 def segmental(x_rows, y_rows, W, P, table=None, track=False, max_n_in=None, ld_t=None, out=None, workspace=None):
@@ -1511,14 +1475,8 @@ def segmental(x_rows, y_rows, W, P, table=None, track=False, max_n_in=None, ld_t
     B = len(n_in)
     K = 0
     if table is not None:
-        for name in ("first", "count", "off"):
-            _chk(table[name], f"segmental table {name}", torch.int32)
-            if table[name].numel() != table["first"].numel() or not table[name].is_contiguous():
-                raise _lib.SwcError(f"segmental: table {name} holds one contiguous entry per band")
-        _chk(table["w"], "segmental table w", torch.float32)
-        if not table["w"].is_contiguous():
-            raise _lib.SwcError("segmental: the table's weights are contiguous")
         K = table["first"].numel()
+        _bank_table("segmental", table, K, "band")
     W, P, K = _segmental_params(W, P, K)
     max_n = max(n_in) if max_n_in is None else int(max_n_in)
     workspace = _workspace("segmental", segmental_workspace_bytes(B, max_n, W, P, K), workspace, device)

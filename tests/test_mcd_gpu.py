@@ -535,3 +535,34 @@ def test_alignment_composes_and_the_tool_runs(tmp_path, capsys):
     assert "alignment: mean |lag| 24.500 samples, largest |lag| 37" in out and "not aligned" not in out
     assert "mean MCD-DTW:" in out and "utt1.wav: MCD-DTW" in out and "over 2 pairs" in out
     assert "alignment" not in plain and "mean MCD:" in plain and "over 2 pairs" in plain
+
+
+def test_audiocodec_mcd_on_the_synthetic_checkpoint():
+    """model.mcd(wavs) is metrics.mcd of the model's own reconstruction against the input, bit for bit, and dtw=, band_ms= and
+    path= reach it"""
+    import common
+    from simwhisper_codec_amd import metrics, synth
+    from simwhisper_codec_amd.codec import AudioCodec
+    dev = device()
+    model = AudioCodec(common.tiny_params(), precision="fp32")
+    model.load_state_dict(common.state_dict("tiny"), strict=True)
+    wavs = [synth.synth_audio(18000, index=0, kind="speech"), synth.synth_audio(17000, index=1, kind="speech")]
+    with pytest.raises(metrics.SwcError, match=r"^mcd: the metrics are HIP kernels \(there is no CPU fallback\)$"):
+        model.mcd(wavs, device="cpu")                                 # the model is still on the host
+    model = model.to(dev).eval()
+    wavs = [w.to(dev) for w in wavs]
+    syn = model.decode(model.encode(wavs)["codes_list"])["syn_wav_list"]
+    got = {}
+    for name, kw in (("warped", {}), ("plain", {"dtw": False}), ("path", {"path": True}), ("band", {"band_ms": 200.0, "path": True})):
+        got[name] = model.mcd(wavs, **kw)
+        want = metrics.mcd(wavs, syn, sample_rate=model.input_sample_rate, device=dev, **kw)
+        assert set(got[name]) == set(want) == {"mcd", "frames_ref", "frames_deg", "steps"} | ({"path"} if kw.get("path") else set()), name
+        for k in want:
+            assert got[name][k].device == dev and poison.same_bits(got[name][k].cpu().contiguous(), want[k].cpu().contiguous()), (name, k)
+    warped, plain = got["warped"], got["plain"]
+    H = metrics.mcd_params(model.input_sample_rate)[1]
+    assert warped["mcd"].shape == (2,) and warped["mcd"].dtype == torch.float32 and not torch.isnan(warped["mcd"]).any()
+    assert warped["frames_ref"].tolist() == [1 + 18000 // H, 1 + 17000 // H]
+    assert plain["steps"].tolist() == torch.minimum(plain["frames_ref"], plain["frames_deg"]).tolist()      # dtw=False: the diagonal
+    assert (warped["steps"] >= torch.maximum(warped["frames_ref"], warped["frames_deg"])).all()            # dtw=True: a path
+    assert poison.same_bits(got["path"]["mcd"].cpu(), warped["mcd"].cpu()) and got["path"]["path"].shape[0] == 2
