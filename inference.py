@@ -115,6 +115,11 @@ def build_parser():
                         "every input before it is encoded (metrics.trimmed: the P.56 activity criterion), so the output has "
                         "the trimmed length; the offsets are logged.  A file in which no speech is found passes untrimmed.  "
                         "Default: off")
+    p.add_argument("--code_stats", type=str, default=None, metavar="PATH.json",
+                   help="--mode encode, single-GPU only: what the codes written use of their codebooks (per group: codes used, "
+                        "utilisation, entropy, perplexity, repeat rate; the effective bitrate beside the nominal one; "
+                        "simwhisper_codec_amd.units.usage) as JSON.  Counted on the GPU, one launch per batch on the batch's "
+                        "stream, read back once at the end.  Default: off, every launch and every file is what it was")
     return p
 
 
@@ -200,6 +205,8 @@ def main(argv=None):
     if world > 1 and args.mode != "roundtrip":
         raise SystemExit(f"--mode {args.mode} runs on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
                          "only --mode roundtrip is data-parallel")
+    if args.code_stats is not None and args.mode != "encode":
+        raise SystemExit(f"--code_stats counts the codes --mode encode writes: it does not go with --mode {args.mode}")
     if world > 1 and args.flac != "host":
         raise SystemExit(f"--flac {args.flac} stages on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
                          "data-parallel runs decode FLAC on the host")
@@ -248,6 +255,12 @@ def main(argv=None):
     level = {} if args.loudness is None else {"loudness": args.loudness, "true_peak_db": args.true_peak_db}
     if args.active_level is not None:
         level = {"active_level": args.active_level}
+
+    stats = None
+    if args.code_stats is not None:
+        from simwhisper_codec_amd import units
+        stats = units.Usage(levels=generator.fsq_levels, groups=generator.num_groups, device=device,
+                            frame_rate=generator.input_sample_rate / generator.encoder_downsample_rate)
 
     def load_one(path):
         return load_file(path, generator.input_sample_rate, on_gpu, args.resample, args.flac)
@@ -335,6 +348,9 @@ def main(argv=None):
                     codes_list, syn = round_trip()
                 if chk.clipped:
                     codes_list, syn = round_trip()
+            if stats is not None:   # the codes that are written, counted on this batch's stream (the counters add up atomically)
+                with torch.cuda.device(device):
+                    stats.add(codes_list)
             out = syn if to_codes else (stager.pcm16_on_device(syn) if on_gpu else [w.cpu() for w in syn])
             if on_gpu:
                 torch.cuda.current_stream().synchronize()
@@ -382,6 +398,13 @@ def main(argv=None):
     if pipe is not None:
         pipe.close()
     io.shutdown()
+    if stats is not None:   # every batch's stream was synchronised before its result was taken
+        import json
+        res = stats.result()
+        with open(args.code_stats, "w") as f:
+            json.dump({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in res.items()}, f, indent=1)
+        logging.info(f"code statistics of {res['frames']} frames written to {args.code_stats}: "
+                     f"{res['bitrate_bps']:.1f} of {res['nominal_bps']:.1f} bit/s")
     dt = time.perf_counter() - t0
     logging.info(f"All audio processing completed: {total_audio:.1f} s of audio in {dt:.2f} s "
                  f"({total_audio / max(dt, 1e-9):.1f} x real time incl. file IO)")

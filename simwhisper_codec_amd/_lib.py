@@ -301,6 +301,18 @@ SUBDTW_SIGNATURES = {
     "swc_subdtw": ([_P, _P, _P, _P, _I, _I, _I, _L, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _L, _P, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_units.h (codebook usage of a batch of code streams; positional agreement and edit distance of two batches), one to
+# one.  The sixteenth table of its own
+UNITS_MAX_GROUPS, UNITS_MAX_CODES = 8, 16384     # SWC_UNITS_MAX_GROUPS / _MAX_CODES
+UNITS_MAX_FRAMES = 8192                          # SWC_UNITS_MAX_FRAMES
+UNITS_CHUNK, UNITS_STRIP = 1024, 256             # SWC_UNITS_CHUNK / _STRIP
+UNITS_USAGE_MAX_FRAMES = 1 << 24                 # SWC_UNITS_USAGE_MAX_FRAMES
+UNITS_SIGNATURES = {
+    "swc_code_usage": ([_P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _I, _P], C.c_int),
+    "swc_code_compare": ([_P, _P, _P, _P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+                         C.c_int),
+}
+
 _lib = None
 
 
@@ -321,7 +333,8 @@ def load():
     # the (argtypes, restype) tables of this library (FLAC_IO_SIGNATURES belongs to the host-side library)
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
-                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES):
+                  LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES,
+                  UNITS_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

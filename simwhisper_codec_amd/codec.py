@@ -1628,6 +1628,42 @@ class AudioCodec(nn.Module):
         return metrics.warpq(wav_list, syn, sample_rate=self.input_sample_rate, patch_ms=patch_ms,
                              steps=metrics.WARPQ_STEPS if steps is None else steps, vad=vad, tracks=tracks, device=dev)
 
+    def _unit_device(self, who, device):
+        dev = self._resolve_device(device)
+        if dev.type != "cuda":
+            raise SwcError(f"{who}: the counting is a HIP kernel (there is no CPU fallback)")
+        return dev
+
+    @_on_model_device
+    @torch.inference_mode()
+    def code_usage(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, codes=False):
+        """What the codes of this audio use of the codebooks: encode -> units.usage with the model's own levels and groups.
+        -> the dict of units.usage_from_counts (used, utilisation, entropy_bits, perplexity, repeat_rate per group, level_hist,
+        bits_per_frame, bitrate_bps against nominal_bps, frames, bad); with codes=True, (that dict, the codes_list)."""
+        from . import units
+        dev = self._unit_device("code_usage", device)
+        codes_list = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+        res = units.usage(codes_list, levels=self.fsq_levels, groups=self.num_groups, device=dev,
+                          frame_rate=self.input_sample_rate / self.encoder_downsample_rate)
+        return (res, codes_list) if codes else res
+
+    @_on_model_device
+    @torch.inference_mode()
+    def code_agreement(self, wav_list, other_wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, dedup=True,
+                       codes=False):
+        """Token robustness: how far apart are the codes of wav_list (the reference: clean input) and of other_wav_list (the
+        same audio degraded, resampled, shifted)?  Both lists are encoded, then units.agreement with the model's own levels.
+        -> the dict of units.agreement (code_match, level_match, level_l1_mean, frame_match, ued, frames and the integer
+        "counts"); with codes=True, (that dict, the reference's codes_list, the other codes_list)."""
+        from . import units
+        if len(wav_list) != len(other_wav_list):
+            raise SwcError(f"code_agreement: {len(wav_list)} reference and {len(other_wav_list)} other waveforms")
+        dev = self._unit_device("code_agreement", device)
+        a = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+        b = self.encode(other_wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+        res = units.agreement(a, b, levels=self.fsq_levels, dedup=dedup, device=dev)
+        return (res, a, b) if codes else res
+
     @_on_model_device
     @torch.inference_mode()
     def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):

@@ -1734,6 +1734,118 @@ def proj_ln(a, w_stream, bias, alpha, x, *, M, N, K, lda=None, x_out=None, ln=No
     return x_out, y_next
 
 
+# ---- token-level measures (include/swc_units.h) ----
+
+def _unit_levels(who, levels):
+    """levels as the host int32[4] the calls take; SwcError for what the library would refuse -> (array, n_codes)"""
+    try:
+        lv = [int(v) for v in levels]
+    except (TypeError, ValueError):
+        lv = []
+    if len(lv) != 4 or any(v < 2 or v > 1024 for v in lv) or math.prod(lv) > _lib.UNITS_MAX_CODES:
+        raise _lib.SwcError(f"{who}: levels must be 4 values in 2..1024 whose product is at most {_lib.UNITS_MAX_CODES}, "
+                            f"got {levels!r}")
+    return (C.c_int32 * 4)(*lv), math.prod(lv)
+
+
+def _unit_shapes(who, codes_list, G, max_frames):
+    """every row a [G, T] int32 or int64 tensor of at most max_frames frames (no CUDA call) -> the frame counts"""
+    for c in codes_list:
+        if not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != G or c.dtype not in (torch.int32, torch.int64):
+            what = f"{tuple(c.shape)} of {c.dtype}" if torch.is_tensor(c) else type(c).__name__
+            raise _lib.SwcError(f"{who}: expected ({G}, T) int32 or int64 code tensors, got {what}")
+    n = [int(c.shape[1]) for c in codes_list]
+    if n and max(n) > max_frames:
+        raise _lib.SwcError(f"{who}: an utterance of {max(n)} frames (at most {max_frames})")
+    return n
+
+
+def _unit_rows(who, codes_list, G, max_frames):
+    """The row checks of a units call, before any launch: _unit_shapes, all rows on one HIP device.  One element size per launch
+    (that of the rows that hold codes, as bitstream.pack_batch); a row of another type or with a column stride is converted.
+    -> (rows, frame counts, element size, device)"""
+    B = len(codes_list)
+    if B == 0 or B > 65535:
+        raise _lib.SwcError(f"{who}: {B} utterances (1..65535)")
+    n = _unit_shapes(who, codes_list, G, max_frames)
+    device = codes_list[0].device
+    if device.type != "cuda" or any(c.device != device for c in codes_list):
+        raise _lib.SwcError(f"{who}: expected tensors on one HIP device (there is no CPU fallback)")
+    kinds = {c.dtype for c, k in zip(codes_list, n) if k}
+    dt = torch.int64 if kinds == {torch.int64} else torch.int32
+    rows = [c if k == 0 or (c.dtype == dt and c.stride(1) == 1) else c.to(dt).contiguous() for c, k in zip(codes_list, n)]
+    return rows, n, 4 if dt == torch.int32 else 8, device
+
+
+def _unit_meta(rows, n):
+    """the address list of one side as host ints: addresses, group strides, frame counts"""
+    return ([r.data_ptr() if k else 0 for r, k in zip(rows, n)] + [r.stride(0) if k else 0 for r, k in zip(rows, n)] + n)
+
+
+def code_usage(codes_list, hist, repeats, totals, levels, max_frames=None):
+    """swc_code_usage: the B utterances of codes_list ([G, T_b] int32 or int64 device tensors, unit column stride; encode()'s
+    strided views as they are) are ADDED into hist int64 [G, n_codes], repeats int64 [G] and totals int64 [2] (the caller
+    zeroes them once).  One small upload (the address list), one call, nothing read back."""
+    lib = _lib.load()
+    lv, n_codes = _unit_levels("code_usage", levels)
+    if hist.dim() != 2 or hist.shape[1] != n_codes or not 1 <= hist.shape[0] <= _lib.UNITS_MAX_GROUPS:
+        raise _lib.SwcError(f"code_usage: hist must be [G, {n_codes}] with G in 1..{_lib.UNITS_MAX_GROUPS}, got {tuple(hist.shape)}")
+    G = int(hist.shape[0])
+    rows, n, es, device = _unit_rows("code_usage", codes_list, G, _lib.UNITS_USAGE_MAX_FRAMES)
+    for t, name, numel in ((hist, "hist", G * n_codes), (repeats, "repeats", G), (totals, "totals", 2)):
+        if t.device != device or t.dtype != torch.int64 or t.numel() != numel or not t.is_contiguous():
+            raise _lib.SwcError(f"code_usage: {name} must be a contiguous int64 tensor of {numel} elements on the codes' device")
+    B = len(rows)
+    mf = max(n) if max_frames is None else int(max_frames)
+    meta = torch.tensor(_unit_meta(rows, n), dtype=torch.int64).to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        _lib.check(lib.swc_code_usage(_ptr(meta[:B]), _ptr(meta[B:2 * B]), _ptr(meta[2 * B:]), es, lv, G, mf, _ptr(hist),
+                                      _ptr(repeats), _ptr(totals), B, _stream()), "swc_code_usage")
+
+
+UNIT_OUTPUTS = ("match", "both_valid", "level_match", "level_l1", "frame_match", "bad", "edit", "len_a", "len_b")
+
+
+def code_compare(codes_a, codes_b, levels, dedup=True, max_frames=None, out=None):
+    """swc_code_compare: pair i = (codes_a[i] the reference, codes_b[i]), [G, T] int32 or int64 device tensors of at most
+    UNITS_MAX_FRAMES frames.  -> dict of int32 device tensors: match, both_valid, edit, len_a, len_b [B, G]; level_match,
+    level_l1 [B, G, 4]; frame_match [B]; bad [B, 2].  out: such a dict of contiguous tensors to write into.  One small
+    upload, one call, nothing read back."""
+    lib = _lib.load()
+    lv, _ = _unit_levels("code_compare", levels)
+    if len(codes_a) != len(codes_b):
+        raise _lib.SwcError(f"code_compare: {len(codes_a)} reference and {len(codes_b)} other code streams")
+    G = int(codes_a[0].shape[0]) if len(codes_a) and torch.is_tensor(codes_a[0]) and codes_a[0].dim() == 2 else 0
+    if not 1 <= G <= _lib.UNITS_MAX_GROUPS:
+        raise _lib.SwcError(f"code_compare: expected (G, T) code tensors with G in 1..{_lib.UNITS_MAX_GROUPS}")
+    ra, na, ea, device = _unit_rows("code_compare", codes_a, G, _lib.UNITS_MAX_FRAMES)
+    rb, nb, eb, dev_b = _unit_rows("code_compare", codes_b, G, _lib.UNITS_MAX_FRAMES)
+    if dev_b != device:
+        raise _lib.SwcError("code_compare: expected both sides on one HIP device")
+    if ea != eb:   # one element size per launch: the int32 side is widened
+        if ea == 4:
+            ra = [r.to(torch.int64).contiguous() if k else r for r, k in zip(ra, na)]
+        else:
+            rb = [r.to(torch.int64).contiguous() if k else r for r, k in zip(rb, nb)]
+        ea = 8
+    B = len(ra)
+    shapes = {"match": (B, G), "both_valid": (B, G), "level_match": (B, G, 4), "level_l1": (B, G, 4), "frame_match": (B,),
+              "bad": (B, 2), "edit": (B, G), "len_a": (B, G), "len_b": (B, G)}
+    if out is None:
+        out = {k: torch.empty(s, dtype=torch.int32, device=device) for k, s in shapes.items()}
+    for k, s in shapes.items():
+        t = out[k]
+        if t.device != device or t.dtype != torch.int32 or tuple(t.shape) != s or not t.is_contiguous():
+            raise _lib.SwcError(f"code_compare: out[{k!r}] must be a contiguous int32 {s} tensor on the codes' device")
+    mf = max(max(na), max(nb)) if max_frames is None else int(max_frames)
+    meta = torch.tensor(_unit_meta(ra, na) + _unit_meta(rb, nb), dtype=torch.int64).to(device, non_blocking=True)
+    m = [_ptr(meta[k * B:(k + 1) * B]) for k in range(6)]
+    with torch.cuda.device(device):
+        _lib.check(lib.swc_code_compare(m[0], m[1], m[2], m[3], m[4], m[5], ea, lv, G, mf, 1 if dedup else 0,
+                                        *[_ptr(out[k]) for k in UNIT_OUTPUTS], B, _stream()), "swc_code_compare")
+    return out
+
+
 def delay_us(us):
     """occupy the current stream for `us` microseconds (phase shift between two streams)"""
     _lib.check(_lib.load().swc_delay_us(int(us), _stream()), "swc_delay_us")
