@@ -14,7 +14,8 @@ batches on the GPU at a time (two streams over one set of weights: same files, m
 `--mode encode` writes the compressed codes instead, `<output_dir>/<basename>.swc` (the SWC1 format of
 simwhisper_codec_amd/bitstream.py: 11 bytes per 80 ms frame, 10 s of audio = 1 387 bytes), and `--mode decode` turns every
 `*.swc` under --input_dir back into `<output_dir>/<basename>.wav`.  With the same file names and --batch_size the two runs
-write the WAV files of one `--mode roundtrip` (the default) run.  Both are single-GPU modes.
+write the WAV files of one `--mode roundtrip` (the default) run.  Both are single-GPU modes.  `--code_format swc2` makes
+`--mode encode` write the entropy-coded, checksummed SWC2 container (include/swc_entropy.h) instead; `--mode decode` reads both.
 
 Several GPUs of one node (BASELINE.json configs[3]): launch the same command under torch.distributed.run
 
@@ -115,6 +116,12 @@ def build_parser():
                         "every input before it is encoded (metrics.trimmed: the P.56 activity criterion), so the output has "
                         "the trimmed length; the offsets are logged.  A file in which no speech is found passes untrimmed.  "
                         "Default: off")
+    p.add_argument("--code_format", type=str, default="swc1", choices=["swc1", "swc2"],
+                   help="--mode encode: the container of the code files written.  swc1 (default): a flat 11 bits per code, every "
+                        "file as before.  swc2: every (utterance, group) stream entropy-coded on the GPU by an adaptive range coder "
+                        "over the FSQ levels, raw where that is shorter, a CRC-32 over the file (include/swc_entropy.h); never "
+                        "larger than the raw codes plus a fixed header.  What it saves on real speech codes has not been "
+                        "measured (no trained checkpoint exists).  --mode decode reads both kinds, also mixed in one directory")
     p.add_argument("--code_stats", type=str, default=None, metavar="PATH.json",
                    help="--mode encode, single-GPU only: what the codes written use of their codebooks (per group: codes used, "
                         "utilisation, entropy, perplexity, repeat rate; the effective bitrate beside the nominal one; "
@@ -207,6 +214,9 @@ def main(argv=None):
                          "only --mode roundtrip is data-parallel")
     if args.code_stats is not None and args.mode != "encode":
         raise SystemExit(f"--code_stats counts the codes --mode encode writes: it does not go with --mode {args.mode}")
+    if args.code_format != "swc1" and args.mode != "encode":
+        raise SystemExit(f"--code_format names the container --mode encode writes: it does not go with --mode {args.mode} "
+                         "(--mode decode tells the two kinds apart by their magic)")
     if world > 1 and args.flac != "host":
         raise SystemExit(f"--flac {args.flac} stages on one GPU: start it without torch.distributed.run (WORLD_SIZE={world}); "
                          "data-parallel runs decode FLAC on the host")
@@ -309,7 +319,8 @@ def main(argv=None):
     def save(paths, wavs):
         t = time.perf_counter()
         if to_codes:   # wavs = bitstream.pack_batch's result: one copy into pinned memory, every file a slice of it
-            list(io.map(save_image, zip(paths, bitstream.images_to_host(wavs))))
+            to_host = bitstream.images2_to_host if args.code_format == "swc2" else bitstream.images_to_host
+            list(io.map(save_image, zip(paths, to_host(wavs))))
         elif flac_out:   # wavs = pcm16_on_device's rows: compressed on the GPU, one copy of the file images into pinned memory
             images = stager.flac_to_host(wavs, generator.output_sample_rate, md5=args.flac_md5 == "device")
             list(io.map(save_flac, zip(paths, images)))
@@ -336,6 +347,8 @@ def main(argv=None):
                 codes = model.encode(wav_list, overlap_seconds=10, device=device, **level)["codes_list"]
                 if to_codes:   # the file images of the batch, packed on the device by one launch (inside the range check)
                     with torch.cuda.device(device):
+                        if args.code_format == "swc2":   # (four launches, nothing read back before the saver thread)
+                            return codes, bitstream.compress_batch(codes, generator.fsq_levels)
                         return codes, bitstream.pack_batch(codes)
                 return codes, model.decode(codes, overlap_seconds=10, device=device)["syn_wav_list"]
             # the range check of the split-f16 encoder is read from a snapshot behind the encode kernels once the decode has been
@@ -371,7 +384,8 @@ def main(argv=None):
             paths, clens, host = fut.result() if hasattr(fut, "result") else fut
             logging.info(f"Encoding completed, code lengths: {clens}")
             if to_codes:
-                logging.info(f"Packing completed, code file sizes: {host[2]} bytes")
+                sizes = host[2].tolist() if torch.is_tensor(host[2]) else host[2]   # (swc2: laid out on the device)
+                logging.info(f"Packing completed, code file sizes: {sizes} bytes")
                 total_audio += sum(clens) * generator.encoder_downsample_rate / generator.input_sample_rate
             else:
                 logging.info(f"Decoding completed, generated waveform lengths: {[len(w) for w in host]} samples")
@@ -439,7 +453,10 @@ def main_decode(args, generator, device):
                 data = f.read()
         except OSError as e:
             raise ValueError(f"{path}: cannot be read ({e})") from e
-        bitstream.parse_header(data, path)
+        if bitstream.is_image2(data):   # an SWC2 file: the CRC is checked here, in the io thread
+            bitstream.parse_image2(data, path)
+        else:
+            bitstream.parse_header(data, path)
         return data
 
     flac_out = args.output_format == "flac"
@@ -468,7 +485,7 @@ def main_decode(args, generator, device):
             blobs = nxt.result()
             nxt = pool.submit(load, batches[bi + 1]) if bi + 1 < len(batches) else None
             with torch.cuda.device(device):
-                _, views, wrong = bitstream.read_images(blobs, paths, device, n_codes=n_codes)
+                _, views, wrong = bitstream.read_images(blobs, paths, device, n_codes=n_codes, levels=generator.fsq_levels)
                 if wrong:
                     raise ValueError(f"{', '.join(paths[i] for i in wrong)}: code values outside the codebook of {n_codes} entries "
                                      "(a corrupt file, or codes of another model)")

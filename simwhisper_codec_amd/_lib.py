@@ -313,6 +313,23 @@ UNITS_SIGNATURES = {
                          C.c_int),
 }
 
+# include/swc_entropy.h (the SWC2 code container: adaptive range coding of every stream and a CRC-32, on the device; the host
+# parser), one to one.  The seventeenth table of its own
+ENTROPY_HEADER_BYTES = 24                        # SWC_ENTROPY_HEADER_BYTES
+ENTROPY_MAX_FRAMES, ENTROPY_MAX_GROUPS = 65536, 8   # SWC_ENTROPY_MAX_FRAMES / _MAX_GROUPS
+ENTROPY_MIN_LEVEL, ENTROPY_MAX_LEVEL, ENTROPY_MAX_CODES = 2, 16, 16384   # SWC_ENTROPY_MIN_LEVEL / _MAX_LEVEL / _MAX_CODES
+ENTROPY_INC, ENTROPY_LIMIT, ENTROPY_MAX_RENORM = 24, 8192, 3   # SWC_ENTROPY_INC / _LIMIT / _MAX_RENORM
+ENTROPY_E = {-1: "not a SWC2 image", -2: "unsupported version", -3: "groups, frames or levels outside the limits",
+             -4: "truncated", -5: "inconsistent stream table", -6: "CRC mismatch"}   # SWC_ENTROPY_E_*
+ENTROPY_SIGNATURES = {
+    "swc_entropy_worst_bytes": ([_L, _I, C.POINTER(C.c_int32)], C.c_int64),
+    "swc_entropy_workspace_bytes": ([C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int64)], C.c_int64),
+    "swc_entropy_encode_batch": ([_P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _P, _L, _P, _P, _P, _P, _L, _I, _P], C.c_int),
+    "swc_entropy_decode_batch": ([_P, _L, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _P, _L, _L, _L, _I, _I, _P, _P], C.c_int),
+    "swc_entropy_parse": ([C.c_char_p, _L, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
+}
+
 _lib = None
 
 
@@ -334,7 +351,7 @@ def load():
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
                   LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES,
-                  UNITS_SIGNATURES):
+                  UNITS_SIGNATURES, ENTROPY_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libswc_hip.so")
 SOURCES = ["swc_api.hip", "swc_gemm.hip", "swc_gemm_skinny.hip", "swc_attention.hip", "swc_attention16.hip", "swc_pointwise.hip", "swc_convnext.hip", "swc_mlp.hip", "swc_convnext64.hip", "swc_projln.hip",
-           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip", "swc_track.hip", "swc_segmental.hip", "swc_subdtw.hip", "swc_units.hip"]
+           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip", "swc_track.hip", "swc_segmental.hip", "swc_subdtw.hip", "swc_units.hip", "swc_entropy.hip"]
 ARCH = "gfx950"
 # per-file flags.  -fno-slp-vectorize: hipcc otherwise packs adjacent f32 mul/add/fma into v_pk_*_f32, which issue at
 # half rate on gfx950 and cost extra v_mov shuffles — slower beside MFMAs (softmax, epilogues)
@@ -46,7 +46,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h", "swc_track.h", "swc_segmental.h", "swc_subdtw.h", "swc_units.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h", "swc_track.h", "swc_segmental.h", "swc_subdtw.h", "swc_units.h", "swc_entropy.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -200,6 +200,31 @@ def build_track_check(force=False):
         raise RuntimeError(f"building swc_track_check failed:\n{r.stdout}")
     os.replace(TRACK_CHECK_PATH + ".tmp", TRACK_CHECK_PATH)
     return TRACK_CHECK_PATH
+
+
+ENTROPY_CHECK_PATH = os.path.join(HERE, "swc_entropy_check")
+
+
+def build_entropy_check(force=False):
+    """swc_entropy_check: a stand-alone host program (its own main) over csrc/swc_entropy_model.h (the range coder, the adaptive
+    model, CRC-32 with its combination and the image parser: the lines swc_entropy.hip runs on the host and in its kernels)
+    compiled with -fsanitize=address,undefined (tests/test_entropy_cpu.py).  No GPU code, nothing preloaded."""
+    src = os.path.join(CSRC, "swc_entropy_check.cpp")
+    deps = [src, os.path.join(CSRC, "swc_entropy_model.h"), os.path.join(ROOT, "include", "swc_entropy.h")]
+    if not force and os.path.exists(ENTROPY_CHECK_PATH) and all(os.path.getmtime(f) <= os.path.getmtime(ENTROPY_CHECK_PATH) for f in deps):
+        return ENTROPY_CHECK_PATH
+    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("g++"), shutil.which("clang++")) if c), None)
+    if cxx is None:
+        raise RuntimeError("no C++ compiler found for swc_entropy_check (set CXX)")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+    base = [cxx, "-std=c++17", "-Wall"] + san + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, src, "-o", ENTROPY_CHECK_PATH + ".tmp"]
+    r = subprocess.run(base + ["-static-libasan", "-static-libubsan"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:   # a toolchain without the runtimes as archives
+        r = subprocess.run(base, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"building swc_entropy_check failed:\n{r.stdout}")
+    os.replace(ENTROPY_CHECK_PATH + ".tmp", ENTROPY_CHECK_PATH)
+    return ENTROPY_CHECK_PATH
 
 
 def stamp_commit():

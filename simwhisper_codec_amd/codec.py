@@ -1666,19 +1666,24 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
-    def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None):
+    def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, format="swc1"):
         """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
         11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one
-        device-to-host copy for the batch."""
+        device-to-host copy for the batch.  format="swc2": the SWC2 images instead (include/swc_entropy.h: every stream
+        entropy-coded on the device, a CRC-32 over the image; never larger than raw plus the header)."""
+        if format not in bitstream.FORMATS:
+            raise SwcError(f"encode_bytes: format {format!r} (one of {bitstream.FORMATS})")
         codes = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
         if not codes:
             return []
+        if format == "swc2":
+            return [v.numpy().tobytes() for v in bitstream.images2_to_host(bitstream.compress_batch(codes, self.fsq_levels))]
         return [v.numpy().tobytes() for v in bitstream.images_to_host(bitstream.pack_batch(codes))]
 
     @_on_model_device
     @torch.inference_mode()
     def decode_bytes(self, blobs, overlap_seconds=10, device=torch.device("cuda")):
-        """decode() from compressed data: blobs = SWC1 file images (bytes-like) -> {"syn_wav_list": [FloatTensor(T_i * 1280)]},
+        """decode() from compressed data: blobs = SWC1 or SWC2 file images (bytes-like) -> {"syn_wav_list": [FloatTensor(T_i * 1280)]},
         the waveforms decode() gives for the codes the images hold.  Headers are checked on the host (ValueError naming the
         blob), one copy and one unpack launch bring the batch to the device, and the decoder does not run before the count
         of values outside this model's codebook is known to be zero: SwcError names the utterances otherwise."""
@@ -1686,7 +1691,9 @@ class AudioCodec(nn.Module):
             return {"syn_wav_list": []}
         dev = self._resolve_device(device)
         n_codes = math.prod(self.fsq_levels)
-        _, views, wrong = bitstream.read_images(blobs, [f"blob {i}" for i in range(len(blobs))], dev, n_codes=n_codes)
+        # (SWC2 images, told by their magic, may be mixed in: their CRC and levels are checked on the host before any launch)
+        _, views, wrong = bitstream.read_images(blobs, [f"blob {i}" for i in range(len(blobs))], dev, n_codes=n_codes,
+                                                levels=self.fsq_levels)
         if wrong:
             raise SwcError(f"decode_bytes: utterances {wrong} hold code values >= {n_codes}, the codebook size of this model "
                            "(corrupt data, or codes of another model)")

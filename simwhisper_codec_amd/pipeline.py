@@ -254,11 +254,19 @@ class HostStager:
             return [i for i in range(len(items)) if st[first[i]:first[i + 1]].any()]
         return out, failed
 
-    def codes_to_host(self, codes_list):
+    def codes_to_host(self, codes_list, format="swc1", levels=None):
         """encode()'s codes_list -> the utterances' SWC1 file images (bitstream.py) as host uint8 views of this thread's pinned
         byte buffer: one pack launch and one device-to-host copy per batch, where bitstream.write_codes costs a launch, a
-        synchronising copy and an allocation per utterance.  The views hold until this thread stages its next batch."""
+        synchronising copy and an allocation per utterance.  The views hold until this thread stages its next batch.
+        format="swc2" (with levels, the model's FSQ levels): the SWC2 images of include/swc_entropy.h instead, entropy-coded and
+        checksummed on the device: four launches, a read-back of the B sizes and one copy."""
         from . import bitstream
+        if format not in bitstream.FORMATS:
+            raise ValueError(f"codes_to_host: format {format!r} (one of {bitstream.FORMATS})")
+        if format == "swc2":
+            if levels is None:
+                raise ValueError("codes_to_host: format='swc2' needs the FSQ levels of the model the codes come from")
+            return bitstream.images2_to_host(bitstream.compress_batch(codes_list, levels), tls=self._tls)
         return bitstream.images_to_host(bitstream.pack_batch(codes_list), tls=self._tls)
 
     def codes_to_device(self, payloads, n_frames, device, n_codes=None, bad=None):

@@ -8,7 +8,8 @@
                                              codes, equal FSQ levels, the mean level distance, equal frames and the unit edit
                                              distance per group; --no_dedup: the plain edit distance, runs not collapsed
 
-The files are read through bitstream.read_codes_batch and counted on the GPU; --json PATH writes the numbers as well."""
+The files (SWC1 or SWC2, also mixed) are read through bitstream.read_codes_batch and counted on the GPU; the first form also
+prints the bytes the files take on disk and the bit rate that is, beside the bits their codes carry; --json PATH writes the numbers as well."""
 import argparse
 import glob
 import json
@@ -62,7 +63,7 @@ def main(argv=None):
     if args.against is None:
         u = units.Usage(levels=args.levels, groups=bitstream.GROUPS, device=device)
         for i in range(0, len(paths), bs):
-            u.add(bitstream.read_codes_batch(paths[i:i + bs], device=device, n_codes=n_codes))
+            u.add(bitstream.read_codes_batch(paths[i:i + bs], device=device, n_codes=n_codes, levels=args.levels))
         r = u.result()
         print(f"{len(paths)} files, {r['frames']} frames, {r['bad']} values outside the codebook of {n_codes}")
         print(f"{'group':>5}{'used':>7}{'util':>8}{'entropy':>9}{'perplexity':>12}{'repeats':>9}")
@@ -70,15 +71,29 @@ def main(argv=None):
             print(f"{g:>5}{r['used'][g]:>7}{r['utilisation'][g]:>8.3f}{r['entropy_bits'][g]:>9.3f}{r['perplexity'][g]:>12.1f}"
                   f"{r['repeat_rate'][g]:>9.3f}")
         print(f"{r['bits_per_frame']:.2f} bits per frame = {r['bitrate_bps']:.1f} bit/s of the nominal {r['nominal_bps']:.1f} bit/s")
+        # what the files take on disk, beside what their codes carry (SWC1 spends a flat 11 bits per code; SWC2 files are
+        # entropy-coded and may come close to bits_per_frame: an adaptive order-1 coder can also go below that order-0 figure)
+        disk = sum(os.path.getsize(p) for p in paths)
+        kinds = {}
+        for p in paths:
+            with open(p, "rb") as f:
+                magic = f.read(4).decode("ascii", "replace")
+            kinds[magic] = kinds.get(magic, 0) + 1
+        rate = r["bitrate_bps"] / r["bits_per_frame"] if r["bits_per_frame"] else float("nan")   # frames per second
+        disk_bpf = 8.0 * disk / r["frames"] if r["frames"] else float("nan")
+        print(f"{disk} bytes on disk ({', '.join(f'{n} {k}' for k, n in sorted(kinds.items()))}), headers included = {disk_bpf:.2f} bits per "
+              f"frame = {disk_bpf * rate:.1f} bit/s")
+        print("(no trained checkpoint exists: what SWC2 saves on real speech codes has not been measured)")
         out = {k: _plain(v) for k, v in r.items()}
+        out.update(bytes_on_disk=disk, disk_bits_per_frame=disk_bpf, disk_bps=disk_bpf * rate, containers=kinds)
     else:
         pairs = pair_up(paths, find(args.against))
         if not pairs:
             raise SystemExit(f"no file under {args.against} has the base name of one under {args.dir}")
         parts = []
         for i in range(0, len(pairs), bs):
-            a = bitstream.read_codes_batch([p for p, _ in pairs[i:i + bs]], device=device, n_codes=n_codes)
-            b = bitstream.read_codes_batch([q for _, q in pairs[i:i + bs]], device=device, n_codes=n_codes)
+            a = bitstream.read_codes_batch([p for p, _ in pairs[i:i + bs]], device=device, n_codes=n_codes, levels=args.levels)
+            b = bitstream.read_codes_batch([q for _, q in pairs[i:i + bs]], device=device, n_codes=n_codes, levels=args.levels)
             parts.append(units.agreement(a, b, levels=args.levels, dedup=not args.no_dedup, device=device))
         c = {k: np.concatenate([p["counts"][k] for p in parts]).astype(np.int64) for k in parts[0]["counts"]}
         frames = np.concatenate([p["frames"] for p in parts])
