@@ -26,6 +26,7 @@ Rank 0 reads and writes the files; every step takes `--batch_size x world` files
 come back to rank 0.  Outputs are the files the single-GPU run writes (sharded decode pads to the global maximum).
 """
 import argparse
+import hashlib
 import logging
 import os
 import sys
@@ -127,7 +128,23 @@ def build_parser():
                         "utilisation, entropy, perplexity, repeat rate; the effective bitrate beside the nominal one; "
                         "simwhisper_codec_amd.units.usage) as JSON.  Counted on the GPU, one launch per batch on the batch's "
                         "stream, read back once at the end.  Default: off, every launch and every file is what it was")
+    p.add_argument("--add_noise_snr", type=float, default=None, metavar="DB",
+                   help="--mode roundtrip / encode, on the GPU and single-GPU only: reproducible white noise is mixed into every "
+                        "input at this signal-to-noise ratio against its P.56 active level before it is encoded "
+                        "(simwhisper_codec_amd.degrade.add_noise; the noise is an Irwin-Hall sum of eight uniforms, not Gaussian).  "
+                        "A file's noise depends on --noise_seed and its base name alone, whatever batch it lands in.  Default: "
+                        "off, every output is what it was")
+    p.add_argument("--noise_seed", type=int, default=0, metavar="N", help="the seed of --add_noise_snr and --reverb_rt60")
+    p.add_argument("--reverb_rt60", type=float, default=None, metavar="S",
+                   help="--mode roundtrip / encode, on the GPU and single-GPU only: every input is convolved with one synthetic room "
+                        "impulse response of this reverberation time (degrade.synthetic_rir under --noise_seed) before the noise "
+                        "is added and before it is encoded; rows keep their length.  Default: off")
     return p
+
+
+def stream_id_of(path):
+    """the noise stream of a file: 64 bits of a hash of its base name, so a file gets the same noise in any batch"""
+    return int.from_bytes(hashlib.blake2b(os.path.basename(path).encode("utf-8"), digest_size=8).digest(), "little")
 
 
 def load_file(path, target_rate, pcm16_ok, resample, flac="host"):
@@ -229,9 +246,16 @@ def main(argv=None):
         raise SystemExit("--active_level and --loudness are two ways to set one level: give one of them")
     if world > 1 and (args.active_level is not None or args.trim_silence):
         raise SystemExit(f"--active_level / --trim_silence run on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
+    degrading = args.add_noise_snr is not None or args.reverb_rt60 is not None
+    if degrading and args.mode == "decode":
+        raise SystemExit("--add_noise_snr / --reverb_rt60 degrade the input of --mode encode and roundtrip; --mode decode reads codes")
+    if degrading and world > 1:
+        raise SystemExit(f"--add_noise_snr / --reverb_rt60 run on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
+    if degrading and device.type != "cuda":
+        raise SystemExit("--add_noise_snr / --reverb_rt60 degrade on the GPU: --device must be a CUDA device")
     if (args.active_level is not None or args.trim_silence) and device.type != "cuda":
         raise SystemExit("--active_level / --trim_silence find the speech on the GPU: --device must be a CUDA device")
     if (args.active_level is not None or args.trim_silence) and args.mode == "decode":
@@ -343,6 +367,14 @@ def main(argv=None):
                     else:
                         logging.info(f"{path}: no speech found, left untrimmed")
                 wav_list = [c if b > a else w for c, w, (a, b) in zip(cut, wav_list, bounds)]
+            if degrading:   # reverberation first, then noise against the reverberant level; nothing is read back
+                from simwhisper_codec_amd import degrade
+                cond = {"seed": args.noise_seed, "stream_ids": [stream_id_of(p) for p in paths]}
+                if args.add_noise_snr is not None:
+                    cond["snr_db"] = args.add_noise_snr
+                if args.reverb_rt60 is not None:
+                    cond["rt60"] = args.reverb_rt60
+                wav_list = degrade.apply(wav_list, [cond], sample_rate=generator.input_sample_rate)[0]
             def round_trip():
                 codes = model.encode(wav_list, overlap_seconds=10, device=device, **level)["codes_list"]
                 if to_codes:   # the file images of the batch, packed on the device by one launch (inside the range check)

@@ -330,6 +330,19 @@ ENTROPY_SIGNATURES = {
                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
 }
 
+# include/swc_degrade.h (reproducible noise, mixing at a signal-to-noise ratio with the gain computed on the device, convolution
+# of a ragged batch with long impulse responses), one to one.  The eighteenth table of its own
+DEGRADE_MAX_TAPS, DEGRADE_BLOCK = 131072, 1024   # SWC_CONV_MAX_TAPS / SWC_CONV_BLOCK
+DEGRADE_MAX_N, DEGRADE_MAX_IRS = 1 << 30, 65535  # SWC_CONV_MAX_N / SWC_CONV_MAX_IRS
+DEGRADE_CHUNK = 4096                             # SWC_DEGRADE_CHUNK
+DEGRADE_UNMIXED, DEGRADE_OVER = 1, 2             # SWC_MIX_UNMIXED / SWC_MIX_OVER
+DEGRADE_SIGNATURES = {
+    "swc_noise": ([C.c_uint64, _P, _P, _L, _P, _L, _L, _I, _P], C.c_int),
+    "swc_mix": ([_P, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _L, _P, _P, _I, _P], C.c_int),
+    "swc_convolve_workspace_bytes": ([_I, _L, _I, _I], C.c_int64),
+    "swc_convolve": ([_P, _P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _L, _L, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -351,7 +364,7 @@ def load():
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
                   LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES,
-                  UNITS_SIGNATURES, ENTROPY_SIGNATURES):
+                  UNITS_SIGNATURES, ENTROPY_SIGNATURES, DEGRADE_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

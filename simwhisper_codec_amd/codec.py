@@ -1666,6 +1666,37 @@ class AudioCodec(nn.Module):
 
     @_on_model_device
     @torch.inference_mode()
+    def robustness(self, wav_list, conditions, sample_rate=16000, dedup=True, overlap_seconds=10, device=torch.device("cuda")):
+        """How far do the tokens move when the same audio comes in noisy or reverberant?  The clean batch (1-D f32 rows at
+        sample_rate on the GPU) is encoded once; for every condition (a dict of degrade.apply: "snr_db", "rt60", "seed", ...)
+        the batch is degraded on the device, encoded, and compared with the clean codes by units.agreement with the model's
+        own levels.  Nothing is read back between degrading and encoding.
+        -> {"conditions": the list, "ued": [C][G] and "code_match": [C][G] (means over the utterances, NaN-free rows only),
+        "frame_match": [C], "counts": the C integer "counts" dicts of units.agreement}.  A condition with neither noise nor
+        reverberation gives ued 0 and matches of 1 exactly."""
+        import numpy as np
+        from . import degrade, units
+        conditions = list(conditions)
+        for cond in conditions:
+            degrade.check_condition("robustness", cond)
+        dev = self._unit_device("robustness", device)
+        clean = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+        res = {"conditions": conditions, "ued": [], "code_match": [], "frame_match": [], "counts": []}
+        for cond in conditions:
+            rows = degrade.apply(wav_list, [cond], sample_rate=sample_rate)[0]
+            codes = self.encode(rows, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
+            a = units.agreement(clean, codes, levels=self.fsq_levels, dedup=dedup, device=dev)
+            with np.errstate(invalid="ignore"):
+                res["ued"].append(np.nanmean(a["ued"], axis=0))
+                res["code_match"].append(np.nanmean(a["code_match"], axis=0))
+                res["frame_match"].append(float(np.nanmean(a["frame_match"])))
+            res["counts"].append(a["counts"])
+        res["ued"], res["code_match"] = np.array(res["ued"]), np.array(res["code_match"])
+        res["frame_match"] = np.array(res["frame_match"])
+        return res
+
+    @_on_model_device
+    @torch.inference_mode()
     def encode_bytes(self, wav_list, overlap_seconds=10, device=torch.device("cuda"), sample_rate=None, format="swc1"):
         """encode() to compressed data: -> list[bytes], utterance i's SWC1 file image (bitstream.py: 12 bytes of header +
         11 bytes per code frame, what bitstream.write_codes(path, codes_list[i]) puts into a file).  One pack launch and one

@@ -1846,6 +1846,151 @@ def code_compare(codes_a, codes_b, levels, dedup=True, max_frames=None, out=None
     return out
 
 
+# ---- degradations (include/swc_degrade.h) ----
+
+def _degrade_rows(who, what, rows):
+    """The row checks of a degrade call, before any launch and without a CUDA call: a non-empty list of at most 65535 1-D f32
+    tensors with unit stride on one HIP device -> (lengths, device)"""
+    B = len(rows)
+    if B == 0 or B > 65535:
+        raise _lib.SwcError(f"{who}: {B} {what} rows (1..65535)")
+    for r in rows:
+        if not torch.is_tensor(r) or r.dtype != torch.float32 or r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
+            got = f"{tuple(r.shape)} of {r.dtype}" if torch.is_tensor(r) else type(r).__name__
+            raise _lib.SwcError(f"{who}: a {what} row is a 1-D f32 tensor with unit stride, got {got}")
+    device = rows[0].device
+    if device.type != "cuda" or any(r.device != device for r in rows):
+        raise _lib.SwcError(f"{who}: expected the {what} rows on one HIP device (the degradations are HIP kernels; there is no CPU "
+                            "fallback)")
+    return [int(r.numel()) for r in rows], device
+
+
+def _degrade_out(who, B, lengths, cols, out, device):
+    """out f32 [B][cols] from torch (cols defaults to the longest row) or the caller's view with unit column stride
+    -> (out, ld, cols)"""
+    if out is None:
+        cols = max(lengths) if cols is None else int(cols)
+        if cols < 0:
+            raise _lib.SwcError(f"{who}: cols={cols}")
+        out = torch.empty((B, cols), device=device, dtype=torch.float32)
+    else:
+        if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != device or out.dim() != 2 or out.shape[0] != B
+                or (out.shape[1] > 1 and out.stride(1) != 1) or (cols is not None and cols != out.shape[1])):
+            raise _lib.SwcError(f"{who}: out must be an f32 [B, cols] tensor on the rows' device with unit column stride")
+        cols = int(out.shape[1])
+    ld = out.stride(0) if B > 1 else max(out.stride(0), cols)
+    if ld < cols:
+        raise _lib.SwcError(f"{who}: out's rows overlap (row stride {ld} < {cols} columns)")
+    return out, ld, cols
+
+
+def _addr(rows, lengths):
+    return [r.data_ptr() if k else 0 for r, k in zip(rows, lengths)]
+
+
+def noise(lengths, seed, stream_ids=None, first=0, cols=None, out=None, device="cuda"):
+    """swc_noise: row b holds lengths[b] samples of the reproducible noise stream (seed, stream_ids[b]) from index `first` on,
+    and zeros behind them -> f32 [B][cols] (cols defaults to the longest row; `out`: an f32 [B, cols] device view with unit
+    column stride to write into).  stream_ids defaults to 0 .. B - 1; ids and seed are taken modulo 2^64.  One small upload
+    (ids and lengths), one call, nothing read back."""
+    try:
+        n = [int(v) for v in lengths]
+        ids = list(range(len(n))) if stream_ids is None else [int(v) for v in stream_ids]
+        seed, first = int(seed) & (2 ** 64 - 1), int(first)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"noise: lengths, stream_ids, seed and first are integers (seed={seed!r}, first={first!r})")
+    B = len(n)
+    if B == 0 or B > 65535 or len(ids) != B or min(n) < 0 or first < 0:
+        raise _lib.SwcError(f"noise: {B} lengths and {len(ids)} stream ids (equal counts in 1..65535, lengths and first >= 0)")
+    device = torch.device(device) if out is None else out.device
+    if device.type != "cuda":
+        raise _lib.SwcError("noise: the generator is a HIP kernel (there is no CPU fallback)")
+    out, ld, cols = _degrade_out("noise", B, n, cols, out, device)
+    signed = [v - 2 ** 64 if v & (2 ** 64 - 1) >= 2 ** 63 else v for v in (i & (2 ** 64 - 1) for i in ids)]
+    meta = torch.tensor(signed + n, dtype=torch.int64).to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().swc_noise(seed, _ptr(meta[:B]), _ptr(meta[B:]), first, _ptr(out), ld, cols, B, _stream()), "swc_noise")
+    return out
+
+
+def _level_column(who, name, t, B, device):
+    """a float64 device column of B levels: a 1-D view (any stride >= 0; a one-element tensor serves every row) -> (tensor, stride)"""
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != device or t.dim() != 1 or t.numel() not in (1, B):
+        raise _lib.SwcError(f"{who}: {name} is a 1-D float64 view of {B} elements (or one) on the rows' device")
+    stride = 0 if t.numel() == 1 and B > 1 else (t.stride(0) if t.numel() > 1 else 1)
+    if stride < 0:
+        raise _lib.SwcError(f"{who}: {name} has a negative stride")
+    return t, stride
+
+
+def mix(x_rows, noise_rows, lx, ln, snr, cols=None, out=None):
+    """swc_mix: out_b[i] = fmaf(noise_b[i mod m_b], g_b, x_b[i]) with g_b = 10^((lx_b - ln_b - snr_b) / 20) computed on the
+    device from three float64 device columns (1-D views of B elements with any stride, e.g. columns of activity()'s values;
+    one element serves every row).  -> (out f32 [B][cols]: the mixture and zeros behind it, gains f32 [B], flags int32 [B]:
+    DEGRADE_UNMIXED = a level or the target is not finite or the noise row is empty (the row is copied), DEGRADE_OVER = the
+    mixture leaves [-1, 1]).  One small upload (the address list), one call, nothing read back."""
+    if len(x_rows) != len(noise_rows):
+        raise _lib.SwcError(f"mix: {len(x_rows)} speech rows and {len(noise_rows)} noise rows")
+    n, device = _degrade_rows("mix", "speech", x_rows)
+    m, dev_v = _degrade_rows("mix", "noise", noise_rows)
+    if dev_v != device:
+        raise _lib.SwcError("mix: expected speech and noise on one HIP device")
+    B = len(n)
+    cols_t = [_level_column("mix", name, t, B, device) for name, t in (("lx", lx), ("ln", ln), ("snr", snr))]
+    out, ld, cols = _degrade_out("mix", B, n, cols, out, device)
+    gains = torch.empty(B, device=device, dtype=torch.float32)
+    flags = torch.empty(B, device=device, dtype=torch.int32)
+    meta = torch.tensor(_addr(x_rows, n) + n + _addr(noise_rows, m) + m, dtype=torch.int64).to(device, non_blocking=True)
+    p = [_ptr(meta[k * B:(k + 1) * B]) for k in range(4)]
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().swc_mix(p[0], p[1], p[2], p[3], _ptr(cols_t[0][0]), cols_t[0][1], _ptr(cols_t[1][0]), cols_t[1][1],
+                               _ptr(cols_t[2][0]), cols_t[2][1], _ptr(out), ld, cols, _ptr(gains), _ptr(flags), B, _stream()), "swc_mix")
+    return out, gains, flags
+
+
+def convolve_workspace_bytes(B, max_n, R, max_L):
+    """swc_convolve_workspace_bytes of include/swc_degrade.h"""
+    return _workspace_bytes(_lib.load().swc_convolve_workspace_bytes(int(B), int(max_n), int(R), int(max_L)), "convolve",
+                            "B={}, max_n={}, R={}, max_L={}", B, max_n, R, max_L)
+
+
+def convolve(x_rows, h_rows, h_index=None, d=0, extra=0, cols=None, max_n=None, out=None, workspace=None):
+    """swc_convolve: y_b[i] = sum_k h_r[k] x_b[i + d - k], r = h_index[b] (a list of B indices into h_rows; None: every row
+    takes h_rows[0]), 0 <= i < min(n_b + extra, cols) -> f32 [B][cols], zeros behind a row's output (cols defaults to the
+    longest row plus extra).  d is the index of the direct path: the output stays aligned with the input.  max_n, out,
+    workspace (tests): the host's length bound, an f32 [B, cols] view to write into, a uint8 workspace to use.  One small
+    upload (the address list), one call, nothing read back."""
+    n, device = _degrade_rows("convolve", "input", x_rows)
+    L, dev_h = _degrade_rows("convolve", "impulse response", h_rows)
+    if dev_h != device:
+        raise _lib.SwcError("convolve: expected the rows and the impulse responses on one HIP device")
+    B, R = len(n), len(L)
+    if min(L) < 1 or max(L) > _lib.DEGRADE_MAX_TAPS:
+        raise _lib.SwcError(f"convolve: an impulse response of {min(L) if min(L) < 1 else max(L)} taps (1..{_lib.DEGRADE_MAX_TAPS})")
+    if h_index is None:
+        if R != 1:
+            raise _lib.SwcError(f"convolve: {R} impulse responses need h_index")
+        idx = [0] * B
+    else:
+        idx = [int(v) for v in h_index]
+        if len(idx) != B or min(idx) < 0 or max(idx) >= R:
+            raise _lib.SwcError(f"convolve: h_index holds {B} indices in 0..{R - 1}")
+    max_L, d, extra = max(L), int(d), int(extra)
+    if not 0 <= d < max_L or not 0 <= extra <= max_L - 1:
+        raise _lib.SwcError(f"convolve: d={d}, extra={extra}: 0 <= d < {max_L} and 0 <= extra <= {max_L - 1} (the longest response)")
+    max_n = max(n) if max_n is None else int(max_n)
+    if not 0 <= max_n <= _lib.DEGRADE_MAX_N:
+        raise _lib.SwcError(f"convolve: a row of {max_n} samples: at most {_lib.DEGRADE_MAX_N} (include/swc_degrade.h)")
+    out, ld, cols = _degrade_out("convolve", B, [k + extra for k in n], cols, out, device)
+    workspace = _workspace("convolve", convolve_workspace_bytes(B, max_n, R, max_L), workspace, device)
+    meta = torch.tensor(_addr(x_rows, n) + n + idx + _addr(h_rows, L) + L, dtype=torch.int64).to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().swc_convolve(_ptr(meta[:B]), _ptr(meta[B:2 * B]), max_n, _ptr(meta[3 * B:3 * B + R]), _ptr(meta[3 * B + R:]), R, max_L,
+                                    _ptr(meta[2 * B:3 * B]), d, extra, _ptr(out), ld, cols, _ptr(workspace), workspace.numel(), B, _stream()),
+                   "swc_convolve")
+    return out
+
+
 def delay_us(us):
     """occupy the current stream for `us` microseconds (phase shift between two streams)"""
     _lib.check(_lib.load().swc_delay_us(int(us), _stream()), "swc_delay_us")
