@@ -139,6 +139,15 @@ def build_parser():
                    help="--mode roundtrip / encode, on the GPU and single-GPU only: every input is convolved with one synthetic room "
                         "impulse response of this reverberation time (degrade.synthetic_rir under --noise_seed) before the noise "
                         "is added and before it is encoded; rows keep their length.  Default: off")
+    p.add_argument("--time_stretch", type=float, default=None, metavar="FACTOR",
+                   help="--mode roundtrip / encode, on the GPU and single-GPU only: every input is played at this speed (above 1: "
+                        "faster and shorter) with its pitch kept, by WSOLA on the device (simwhisper_codec_amd.degrade.time_stretch), "
+                        "before reverberation and noise and before it is encoded.  A file's result does not depend on the batch it "
+                        "lands in.  Default: off, every output is what it was")
+    p.add_argument("--pitch_shift", type=float, default=None, metavar="SEMITONES",
+                   help="--mode roundtrip / encode, on the GPU and single-GPU only: every input's pitch is moved by this many "
+                        "semitones (at most 12 up or down) and its length kept (degrade.pitch_shift: stretch, then resample), "
+                        "before reverberation and noise and before it is encoded.  Default: off")
     return p
 
 
@@ -251,11 +260,24 @@ def main(argv=None):
         raise SystemExit("--add_noise_snr / --reverb_rt60 degrade the input of --mode encode and roundtrip; --mode decode reads codes")
     if degrading and world > 1:
         raise SystemExit(f"--add_noise_snr / --reverb_rt60 run on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
+    stretching = args.time_stretch is not None or args.pitch_shift is not None
+    if stretching and args.mode == "decode":
+        raise SystemExit("--time_stretch / --pitch_shift degrade the input of --mode encode and roundtrip; --mode decode reads codes")
+    if stretching and world > 1:
+        raise SystemExit(f"--time_stretch / --pitch_shift run on one GPU: start it without torch.distributed.run (WORLD_SIZE={world})")
     if world > 1:
         return main_distributed(args, world)
     device = torch.device(args.device)
     if degrading and device.type != "cuda":
         raise SystemExit("--add_noise_snr / --reverb_rt60 degrade on the GPU: --device must be a CUDA device")
+    if stretching and device.type != "cuda":
+        raise SystemExit("--time_stretch / --pitch_shift degrade on the GPU: --device must be a CUDA device")
+    if stretching:   # the values' own refusals, before anything is loaded
+        from simwhisper_codec_amd import degrade
+        try:
+            degrade.check_condition("inference", {"speed": args.time_stretch, "semitones": args.pitch_shift})
+        except degrade.SwcError as e:
+            raise SystemExit(str(e))
     if (args.active_level is not None or args.trim_silence) and device.type != "cuda":
         raise SystemExit("--active_level / --trim_silence find the speech on the GPU: --device must be a CUDA device")
     if (args.active_level is not None or args.trim_silence) and args.mode == "decode":
@@ -367,9 +389,13 @@ def main(argv=None):
                     else:
                         logging.info(f"{path}: no speech found, left untrimmed")
                 wav_list = [c if b > a else w for c, w, (a, b) in zip(cut, wav_list, bounds)]
-            if degrading:   # reverberation first, then noise against the reverberant level; nothing is read back
+            if degrading or stretching:   # stretch or shift, reverberation, then noise against the reverberant level; nothing is read back
                 from simwhisper_codec_amd import degrade
                 cond = {"seed": args.noise_seed, "stream_ids": [stream_id_of(p) for p in paths]}
+                if args.time_stretch is not None:
+                    cond["speed"] = args.time_stretch
+                if args.pitch_shift is not None:
+                    cond["semitones"] = args.pitch_shift
                 if args.add_noise_snr is not None:
                     cond["snr_db"] = args.add_noise_snr
                 if args.reverb_rt60 is not None:

@@ -343,6 +343,18 @@ DEGRADE_SIGNATURES = {
     "swc_convolve": ([_P, _P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _L, _L, _P, _L, _I, _P], C.c_int),
 }
 
+# include/swc_stretch.h (WSOLA time stretch of a ragged batch with a least-squares search in exact integer arithmetic), one to
+# one.  The nineteenth table of its own
+STRETCH_MIN_W, STRETCH_MAX_W, STRETCH_MAX_D = 16, 2048, 1024   # SWC_STRETCH_MIN_W / _MAX_W / _MAX_D
+STRETCH_MAX_TERM, STRETCH_MAX_RATIO = 65535, 4                 # SWC_STRETCH_MAX_TERM / _MAX_RATIO
+STRETCH_MAX_N, STRETCH_CHUNK = 1 << 22, 4096                   # SWC_STRETCH_MAX_N / SWC_STRETCH_CHUNK
+STRETCH_UNDEFINED = 1                                          # SWC_STRETCH_UNDEFINED
+STRETCH_SIGNATURES = {
+    "swc_stretch_out_len": ([_L, _I, _I], C.c_int64),
+    "swc_stretch_workspace_bytes": ([_I, _L, _I, _I, _I], C.c_int64),
+    "swc_stretch": ([_P, _P, _L, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P, _P, _L, _I, _P], C.c_int),
+}
+
 _lib = None
 
 
@@ -364,7 +376,7 @@ def load():
     for table in (PLAIN, AUDIO_SIGNATURES, CODES_SIGNATURES, METRICS_SIGNATURES, QUALITY_SIGNATURES, FLAC_SIGNATURES,
                   FLAC_ENC_SIGNATURES, SPECTRAL_SIGNATURES, PITCH_SIGNATURES, ALIGN_SIGNATURES, MCD_SIGNATURES,
                   LOUDNESS_SIGNATURES, ACTIVITY_SIGNATURES, TRACK_SIGNATURES, SEGMENTAL_SIGNATURES, SUBDTW_SIGNATURES,
-                  UNITS_SIGNATURES, ENTROPY_SIGNATURES, DEGRADE_SIGNATURES):
+                  UNITS_SIGNATURES, ENTROPY_SIGNATURES, DEGRADE_SIGNATURES, STRETCH_SIGNATURES):
         for name, (argtypes, restype) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libswc_hip.so")
 SOURCES = ["swc_api.hip", "swc_gemm.hip", "swc_gemm_skinny.hip", "swc_attention.hip", "swc_attention16.hip", "swc_pointwise.hip", "swc_convnext.hip", "swc_mlp.hip", "swc_convnext64.hip", "swc_projln.hip",
-           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip", "swc_track.hip", "swc_segmental.hip", "swc_subdtw.hip", "swc_units.hip", "swc_entropy.hip", "swc_degrade.hip"]
+           "swc_resample.hip", "swc_codes.hip", "swc_stoi.hip", "swc_flac_gpu.hip", "swc_flac_enc.hip", "swc_spectral.hip", "swc_pitch.hip", "swc_align.hip", "swc_mcd.hip", "swc_loudness.hip", "swc_activity.hip", "swc_track.hip", "swc_segmental.hip", "swc_subdtw.hip", "swc_units.hip", "swc_entropy.hip", "swc_degrade.hip", "swc_stretch.hip"]
 ARCH = "gfx950"
 # per-file flags.  -fno-slp-vectorize: hipcc otherwise packs adjacent f32 mul/add/fma into v_pk_*_f32, which issue at
 # half rate on gfx950 and cost extra v_mov shuffles — slower beside MFMAs (softmax, epilogues)
@@ -32,7 +32,10 @@ EXTRA_FLAGS = {"swc_attention16.hip": ["-fno-slp-vectorize"], "swc_convnext.hip"
                # include/swc_segmental.h as well (Levinson, the quadratic forms, the cepstra: one rounding per operation)
                "swc_segmental.hip": ["-ffp-contract=off"],
                # include/swc_subdtw.h: the float64 sums, the variance and the division of swc_cmvn round once per operation
-               "swc_subdtw.hip": ["-ffp-contract=off"]}
+               "swc_subdtw.hip": ["-ffp-contract=off"],
+               # include/swc_stretch.h: the output expression states its own fma (one rounded product, one fmaf) and the window
+               # is rounded once; nothing else in that file may contract
+               "swc_stretch.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():
@@ -46,7 +49,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h", "swc_track.h", "swc_segmental.h", "swc_subdtw.h", "swc_units.h", "swc_entropy.h", "swc_degrade.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "include", h) for h in ("swc.h", "swc_audio.h", "swc_codes.h", "swc_metrics.h", "swc_quality.h", "swc_flac.h", "swc_flac_enc.h", "swc_spectral.h", "swc_pitch.h", "swc_align.h", "swc_mcd.h", "swc_loudness.h", "swc_activity.h", "swc_track.h", "swc_segmental.h", "swc_subdtw.h", "swc_units.h", "swc_entropy.h", "swc_degrade.h", "swc_stretch.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

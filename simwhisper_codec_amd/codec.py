@@ -1673,12 +1673,14 @@ class AudioCodec(nn.Module):
         own levels.  Nothing is read back between degrading and encoding.
         -> {"conditions": the list, "ued": [C][G] and "code_match": [C][G] (means over the utterances, NaN-free rows only),
         "frame_match": [C], "counts": the C integer "counts" dicts of units.agreement}.  A condition with neither noise nor
-        reverberation gives ued 0 and matches of 1 exactly."""
+        reverberation gives ued 0 and matches of 1 exactly.  A condition with a "speed" other than 1 (degrade.time_stretch)
+        gives streams of another length: ued as ever, NaN for code_match and frame_match, which compare position by position;
+        "semitones" and "pitch_ratio" (degrade.pitch_shift) keep the length and all three."""
         import numpy as np
         from . import degrade, units
         conditions = list(conditions)
         for cond in conditions:
-            degrade.check_condition("robustness", cond)
+            degrade.check_condition("robustness", cond, sample_rate)
         dev = self._unit_device("robustness", device)
         clean = self.encode(wav_list, overlap_seconds=overlap_seconds, device=device, sample_rate=sample_rate)["codes_list"]
         res = {"conditions": conditions, "ued": [], "code_match": [], "frame_match": [], "counts": []}
@@ -1688,8 +1690,12 @@ class AudioCodec(nn.Module):
             a = units.agreement(clean, codes, levels=self.fsq_levels, dedup=dedup, device=dev)
             with np.errstate(invalid="ignore"):
                 res["ued"].append(np.nanmean(a["ued"], axis=0))
-                res["code_match"].append(np.nanmean(a["code_match"], axis=0))
-                res["frame_match"].append(float(np.nanmean(a["frame_match"])))
+                if degrade.condition_speed(cond) is None:
+                    res["code_match"].append(np.nanmean(a["code_match"], axis=0))
+                    res["frame_match"].append(float(np.nanmean(a["frame_match"])))
+                else:   # another speed: the streams differ in length, and position k of one is not position k of the other
+                    res["code_match"].append(np.full(np.shape(a["code_match"])[1:], np.nan))
+                    res["frame_match"].append(float("nan"))
             res["counts"].append(a["counts"])
         res["ued"], res["code_match"] = np.array(res["ued"]), np.array(res["code_match"])
         res["frame_match"] = np.array(res["frame_match"])

@@ -2,8 +2,11 @@
 P.56 active level or the long-term level, synthetic room impulse responses and the reverberation of a ragged batch, and
 apply(), which runs a list of conditions.  This is the producer side of units.agreement: the same audio, noisy or reverberant,
 made on the device, bit for bit the same for the same seed.  Nothing is read back but the one small row synthetic_rir needs
-for drr_db.  The noise is an Irwin-Hall sum of eight uniforms (close to Gaussian, no tails: include/swc_degrade.h)."""
+for drr_db.  The noise is an Irwin-Hall sum of eight uniforms (close to Gaussian, no tails: include/swc_degrade.h).
+time_stretch and pitch_shift (include/swc_stretch.h: WSOLA with a least-squares search in exact integer arithmetic, and a
+resampler behind it) are the other two perturbations: the same audio faster, slower or at another pitch."""
 import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -158,13 +161,158 @@ def reverberate(wav_list, rir=None, rt60=None, tail=False, d=0, sample_rate=1600
     return _rows_of(out, n)
 
 
-CONDITION_KEYS = ("snr_db", "rt60", "seed", "level", "drr_db", "predelay_ms", "noise", "rir", "d", "stream_ids")
+# ---- time stretch and pitch shift (include/swc_stretch.h) ----
+
+MAX_SEMITONES = 12.0
 
 
-def check_condition(who, cond):
-    """the refusals of one condition, before any launch"""
+def _speed_fraction(who, speed):
+    """a speed as the fraction the kernel takes: Fraction(speed).limit_denominator(1000), inside the header's limits"""
+    if isinstance(speed, bool) or not isinstance(speed, (int, float, np.integer, np.floating, Fraction)):
+        raise SwcError(f"{who}: speed={speed!r}: a finite number > 0")
+    if not isinstance(speed, Fraction) and not math.isfinite(float(speed)):
+        raise SwcError(f"{who}: speed={speed!r}: a finite number > 0")
+    if not speed > 0:
+        raise SwcError(f"{who}: speed={speed!r}: a finite number > 0")
+    f = Fraction(speed if isinstance(speed, Fraction) else float(speed)).limit_denominator(1000)
+    R = _lib.STRETCH_MAX_RATIO
+    if f <= 0 or f > R or f * R < 1 or f.numerator > _lib.STRETCH_MAX_TERM:
+        raise SwcError(f"{who}: speed={speed!r}: between 1/{R} and {R} (include/swc_stretch.h)")
+    return f
+
+
+def _stretch_window(who, window_ms, search_ms, sample_rate):
+    """-> (W, D) in samples: the window rounded up to a multiple of 8, the search half-range rounded to the nearest sample"""
+    window_ms, search_ms = _finite(who, "window_ms", window_ms), _finite(who, "search_ms", search_ms)
+    try:
+        fs = int(sample_rate)
+    except (TypeError, ValueError):
+        fs = 0
+    if fs < 1:
+        raise SwcError(f"{who}: sample_rate={sample_rate!r}: a rate >= 1")
+    W = -(-int(math.ceil(window_ms * fs / 1000.0)) // 8) * 8
+    D = int(round(search_ms * fs / 1000.0))
+    if not _lib.STRETCH_MIN_W <= W <= _lib.STRETCH_MAX_W or not 0 <= D <= _lib.STRETCH_MAX_D:
+        raise SwcError(f"{who}: window_ms={window_ms!r}, search_ms={search_ms!r} at {fs} Hz give W={W}, D={D}: W in "
+                       f"{_lib.STRETCH_MIN_W}..{_lib.STRETCH_MAX_W}, D in 0..{_lib.STRETCH_MAX_D} (include/swc_stretch.h)")
+    return W, D
+
+
+def time_stretch(wav_list, speed, window_ms=32.0, search_ms=8.0, sample_rate=16000, tracks=False):
+    """Every row played at `speed` (a number, or one per row; above 1: faster and shorter) with its pitch kept, by WSOLA on the
+    device (ops.stretch).  The speed is taken as Fraction(speed).limit_denominator(1000); rows are grouped by that value, one
+    call per distinct value.  The window is window_ms rounded up to a multiple of 8 samples, the search half-range search_ms.
+    Row b comes out with ceil(n_b / speed) samples.  Nothing is read back, so a row that holds a NaN or an Inf is not reported
+    here: it comes out as zeros of that length, with positions 0 (ops.stretch's "flags" name such rows).
+    -> list of 1-D f32 device rows; with tracks=True, (rows, positions: list of 1-D int32 device rows, s_m per frame)"""
+    B = len(wav_list)
+    if isinstance(speed, (list, tuple, np.ndarray)):
+        if len(speed) != B:
+            raise SwcError(f"time_stretch: {len(speed)} values of speed for {B} waveforms")
+        speeds = [_speed_fraction("time_stretch", v) for v in speed]
+    else:
+        speeds = [_speed_fraction("time_stretch", speed)] * B
+    W, D = _stretch_window("time_stretch", window_ms, search_ms, sample_rate)
+    wav_list = _wavs("time_stretch", wav_list)
+    device = wav_list[0].device
+    rows, pos = [None] * B, [None] * B
+    want = ("out", "pos") if tracks else ("out",)
+    for f in sorted(set(speeds)):
+        idx = [b for b in range(B) if speeds[b] == f]
+        group = [wav_list[b] for b in idx]
+        with torch.cuda.device(device):
+            res = ops.stretch(group, f.numerator, f.denominator, W=W, D=D, want=want)
+        for k, b in enumerate(idx):
+            n_out = -(-int(group[k].numel()) * f.denominator // f.numerator)
+            rows[b] = res["out"][k, :n_out]
+            if tracks:
+                pos[b] = res["pos"][k, :-(-n_out // (W // 2))]
+    return (rows, pos) if tracks else rows
+
+
+def _pitch_ratio(who, semitones, ratio):
+    """-> (r asked for, Fraction p/q realised)"""
+    if (semitones is None) == (ratio is None):
+        raise SwcError(f"{who}: give semitones= or ratio= (one of them)")
+    if semitones is not None:
+        semitones = _finite(who, "semitones", semitones)
+        if abs(semitones) > MAX_SEMITONES:
+            raise SwcError(f"{who}: semitones={semitones!r}: at most {MAX_SEMITONES:g} up or down")
+        r = 2.0 ** (semitones / 12.0)
+    else:
+        r = _finite(who, "ratio", ratio)
+        if not 0.5 <= r <= 2.0:
+            raise SwcError(f"{who}: ratio={ratio!r}: between 0.5 and 2 (an octave down or up)")
+    return r, Fraction(r).limit_denominator(64)
+
+
+def _resample_table_fits(who, p, q):
+    """the host's check that the filter of the resampling p -> q fits the resampler's LDS tile (include/swc_audio.h), with the
+    packing rule of ops.pack_resample_table on the host's numbers: nothing is launched"""
+    from . import wavio
+    from .metrics import RESAMPLE_MAX_LDS_FLOATS
+    if p == q:
+        return
+    K, orig, new, width = wavio.resample_taps(p, q)
+    taps = K.shape[1]
+    nz, at = K != 0, torch.arange(taps)
+    run = max(int((torch.where(nz, at, -1).amax(dim=1) - torch.where(nz, at, taps).amin(dim=1)).max()) + 1, 1)
+    floats = (255 // new + 1) * orig + taps + min(new, 256) * ((run | 1) + 1)
+    if floats > RESAMPLE_MAX_LDS_FLOATS:
+        raise SwcError(f"{who}: the filter of the ratio {p}/{q} ({run} taps per phase) needs {floats} f32 words of LDS per resampler "
+                       f"tile, RESAMPLE_MAX_LDS_FLOATS = {RESAMPLE_MAX_LDS_FLOATS} fit")
+
+
+def pitch_shift(wav_list, semitones=None, ratio=None, window_ms=32.0, search_ms=8.0, sample_rate=16000):
+    """Every row's pitch moved by `semitones` (at most 12 up or down) or by the frequency ratio `ratio`, its length kept: the
+    ratio r is taken as p / q = Fraction(r).limit_denominator(64); the rows are stretched at the speed q / p (time_stretch),
+    resampled from p to q (ops.resample) and cut or zero-padded to the input's length.  Formants move with the pitch.  A row
+    that holds a NaN or an Inf comes out as zeros, as from time_stretch.
+    -> (rows: list of 1-D f32 device rows, info: dict(p, q, ratio = p / q, asked = r, cents_error = 1200 log2((p / q) / r)))"""
+    r, f = _pitch_ratio("pitch_shift", semitones, ratio)
+    p, q = f.numerator, f.denominator
+    W, D = _stretch_window("pitch_shift", window_ms, search_ms, sample_rate)
+    _resample_table_fits("pitch_shift", p, q)
+    wav_list = _wavs("pitch_shift", wav_list)
+    device = wav_list[0].device
+    n = [int(w.numel()) for w in wav_list]
+    info = {"p": p, "q": q, "ratio": p / q, "asked": r, "cents_error": 1200.0 * math.log2((p / q) / r)}
+    with torch.cuda.device(device):
+        out = ops.stretch(wav_list, q, p, W=W, D=D, want=("out",))["out"]
+        slow = [out[b, :-(-k * p // q)] for b, k in enumerate(n)]
+        if p == q:
+            return slow, info
+        out = ops.resample(slow, p, q, cols=max(n))[0]
+    return _rows_of(out, n), info
+
+
+CONDITION_KEYS = ("snr_db", "rt60", "seed", "level", "drr_db", "predelay_ms", "noise", "rir", "d", "stream_ids", "speed", "semitones",
+                  "pitch_ratio", "window_ms", "search_ms")
+
+
+def condition_speed(cond):
+    """the speed of a condition as a Fraction, None where it has none or the speed is 1: the row keeps its length and its
+    frames then, and a comparison frame by frame has a meaning"""
+    if cond.get("speed") is None:
+        return None
+    f = _speed_fraction("condition", cond["speed"])
+    return None if f == 1 else f
+
+
+def _condition_window(cond):
+    return (32.0 if cond.get("window_ms") is None else cond["window_ms"], 8.0 if cond.get("search_ms") is None else cond["search_ms"])
+
+
+def check_condition(who, cond, sample_rate=16000):
+    """the refusals of one condition, before any launch; sample_rate: the rate "window_ms" and "search_ms" are taken at"""
     if not isinstance(cond, dict) or any(k not in CONDITION_KEYS for k in cond):
         raise SwcError(f"{who}: a condition is a dict with keys out of {CONDITION_KEYS}, got {cond!r}")
+    if cond.get("speed") is not None:
+        _speed_fraction(who, cond["speed"])
+    if cond.get("semitones") is not None or cond.get("pitch_ratio") is not None:
+        _pitch_ratio(who, cond.get("semitones"), cond.get("pitch_ratio"))
+    if cond.get("window_ms") is not None or cond.get("search_ms") is not None:
+        _stretch_window(who, *_condition_window(cond), sample_rate)
     if cond.get("snr_db") is not None and not isinstance(cond["snr_db"], (list, tuple, np.ndarray)):
         _finite(who, "snr_db", cond["snr_db"])
     if cond.get("rt60") is not None and not _finite(who, "rt60", cond["rt60"]) > 0:
@@ -174,15 +322,24 @@ def check_condition(who, cond):
 
 
 def apply(wav_list, conditions, sample_rate=16000):
-    """Every condition applied to the batch: reverberation first ("rt60", or "rir" with "d"; rows keep their length), then noise
-    at "snr_db" against the reverberant level ("seed", "level", "noise", "stream_ids" as in add_noise; "drr_db", "predelay_ms"
-    as in synthetic_rir).  A condition with neither returns the rows as they are.  -> one list of rows per condition"""
+    """Every condition applied to the batch: the time stretch ("speed"; a speed of 1 is the identity and runs nothing) and the
+    pitch shift ("semitones" or "pitch_ratio") first, both with "window_ms" and "search_ms" as in time_stretch, then
+    reverberation ("rt60", or "rir" with "d"; rows keep their length), then noise at "snr_db" against the reverberant level
+    ("seed", "level", "noise", "stream_ids" as in add_noise; "drr_db", "predelay_ms" as in synthetic_rir).  A condition with
+    none of them returns the rows as they are.  -> one list of rows per condition"""
     for cond in conditions:
-        check_condition("apply", cond)
+        check_condition("apply", cond, sample_rate)
     wav_list = _wavs("apply", wav_list)
     res = []
     for cond in conditions:
         rows, seed = wav_list, cond.get("seed", 0)
+        if condition_speed(cond) is not None:
+            window_ms, search_ms = _condition_window(cond)
+            rows = time_stretch(rows, condition_speed(cond), window_ms=window_ms, search_ms=search_ms, sample_rate=sample_rate)
+        if cond.get("semitones") is not None or cond.get("pitch_ratio") is not None:
+            window_ms, search_ms = _condition_window(cond)
+            rows = pitch_shift(rows, semitones=cond.get("semitones"), ratio=cond.get("pitch_ratio"), window_ms=window_ms,
+                               search_ms=search_ms, sample_rate=sample_rate)[0]
         if cond.get("rt60") is not None:
             rows = reverberate(rows, rt60=cond["rt60"], sample_rate=sample_rate, seed=seed, drr_db=cond.get("drr_db"),
                                predelay_ms=cond.get("predelay_ms", 0.0))

@@ -1991,6 +1991,91 @@ def convolve(x_rows, h_rows, h_index=None, d=0, extra=0, cols=None, max_n=None, 
     return out
 
 
+# ---- time stretch (include/swc_stretch.h) ----
+
+STRETCH_OUTPUTS = ("out", "pos", "dist", "flags")
+
+
+def _stretch_params(who, num, den, W, D):
+    """the refusals of a stretch call's parameters, before the library is touched -> (num, den, W, D) as ints"""
+    try:
+        num, den, W, D = int(num), int(den), int(W), int(D)
+    except (TypeError, ValueError):
+        raise _lib.SwcError(f"{who}: num, den, W and D are integers")
+    T, R = _lib.STRETCH_MAX_TERM, _lib.STRETCH_MAX_RATIO
+    if not (1 <= num <= T and 1 <= den <= T and num <= R * den and den <= R * num):
+        raise _lib.SwcError(f"{who}: speed {num}/{den}: terms in 1..{T} and 1/{R} <= num/den <= {R} (include/swc_stretch.h)")
+    if not _lib.STRETCH_MIN_W <= W <= _lib.STRETCH_MAX_W or W % 8:
+        raise _lib.SwcError(f"{who}: W={W}: a multiple of 8 in {_lib.STRETCH_MIN_W}..{_lib.STRETCH_MAX_W}")
+    if not 0 <= D <= _lib.STRETCH_MAX_D:
+        raise _lib.SwcError(f"{who}: D={D} (0..{_lib.STRETCH_MAX_D})")
+    return num, den, W, D
+
+
+def stretch_out_len(n, num, den):
+    """ceil(n den / num): swc_stretch_out_len of include/swc_stretch.h"""
+    v = int(_lib.load().swc_stretch_out_len(int(n), int(num), int(den)))
+    if v < 0:
+        raise _lib.SwcError(f"stretch: no output length for n={n}, speed {num}/{den} (include/swc_stretch.h)")
+    return v
+
+
+def stretch_workspace_bytes(B, max_n, W, num, den):
+    """swc_stretch_workspace_bytes of include/swc_stretch.h"""
+    return _workspace_bytes(_lib.load().swc_stretch_workspace_bytes(int(B), int(max_n), int(W), int(num), int(den)), "stretch",
+                            "B={}, max_n={}, W={}, speed {}/{}", B, max_n, W, num, den)
+
+
+def stretch(x_rows, num, den, W=512, D=128, want=("out", "pos", "flags"), cols=None, max_n=None, out=None, workspace=None):
+    """swc_stretch: every row played at the speed num / den (above 1: shorter) without a change of pitch, by WSOLA with the
+    window W and the search half-range D in samples -> dict of the wanted outputs: out f32 [B][cols] (row b holds its
+    ceil(n_b den / num) samples and zeros behind them; cols defaults to the longest), pos int32 [B][Jmax] = the read position
+    s_m of every frame, dist int64 [B][Jmax] = the least squares reached there, flags int32 [B] = STRETCH_UNDEFINED for a row
+    with a NaN or an Inf.  `out` (tests): a dict of tensors to write into, "out" an f32 [B, cols] view with unit column
+    stride, "pos" / "dist" 2-D views with unit column stride (their row stride is ldm); max_n, workspace (tests): the host's
+    length bound and a uint8 workspace to use.  One small upload (the address list), one call, nothing read back."""
+    want = _want("stretch", want, STRETCH_OUTPUTS)
+    num, den, W, D = _stretch_params("stretch", num, den, W, D)
+    n, device = _degrade_rows("stretch", "input", x_rows)
+    B = len(n)
+    max_n = max(n) if max_n is None else int(max_n)
+    if not 0 <= max_n <= _lib.STRETCH_MAX_N:
+        raise _lib.SwcError(f"stretch: a row of {max_n} samples: at most {_lib.STRETCH_MAX_N} (include/swc_stretch.h)")
+    given = dict(out or {})
+    if any(k not in want for k in given):
+        raise _lib.SwcError(f"stretch: out= holds {tuple(given)}, want={want}")
+    n_out = [-(-min(k, max_n) * den // num) for k in n]
+    Jmax = -(-(-(-max_n * den // num)) // (W // 2))
+    res, ld, ldm = {}, 0, Jmax
+    if "out" in want:
+        res["out"], ld, cols = _degrade_out("stretch", B, n_out, cols, given.get("out"), device)
+    else:
+        cols = 0
+    for name, dtype in (("pos", torch.int32), ("dist", torch.int64)):
+        if name in want:
+            t = given.get(name)
+            if t is None:
+                t = torch.empty((B, Jmax), device=device, dtype=dtype)
+            if (not torch.is_tensor(t) or t.dtype != dtype or t.device != device or t.dim() != 2 or t.shape[0] != B or t.shape[1] < Jmax
+                    or (t.shape[1] > 1 and t.stride(1) != 1)):
+                raise _lib.SwcError(f"stretch: {name} must be a {dtype} [B, >= {Jmax}] tensor on the rows' device with unit column stride")
+            res[name] = t
+    strides = {max(res[k].stride(0), res[k].shape[1]) if B == 1 else res[k].stride(0) for k in ("pos", "dist") if k in res}
+    if len(strides) > 1:
+        raise _lib.SwcError("stretch: pos and dist share one row stride (ldm)")
+    if strides:
+        ldm = strides.pop()
+    if "flags" in want:
+        res["flags"] = _outputs("stretch", {"flags": ((B,), torch.int32)}, given, device, torch.empty)["flags"]
+    workspace = _workspace("stretch", stretch_workspace_bytes(B, max_n, W, num, den), workspace, device)
+    meta = torch.tensor(_addr(x_rows, n) + n, dtype=torch.int64).to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().swc_stretch(_ptr(meta[:B]), _ptr(meta[B:]), max_n, W, D, num, den, _ptr(res.get("out")), ld, cols,
+                                           _ptr(res.get("pos")), _ptr(res.get("dist")), ldm, _ptr(res.get("flags")), _ptr(workspace),
+                                           workspace.numel(), B, _stream()), "swc_stretch")
+    return res
+
+
 def delay_us(us):
     """occupy the current stream for `us` microseconds (phase shift between two streams)"""
     _lib.check(_lib.load().swc_delay_us(int(us), _stream()), "swc_delay_us")
